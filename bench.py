@@ -12,13 +12,27 @@ Multi-GPU (weak scaling): one process per GPU, replicated index, each rank
 matches its own 100M-topic slice; no collective on the data path.  `value` is
 the topics of all ranks / the max-over-ranks wall time.
 
-Also reported: a roofline object for the dominant kernel (k_match_fused:
-tokenizer + trie walk, algorithmic bytes per SURVEY.md §8d ÷ its HIP-event time), a CPU
-baseline (the oracle's faithful emqx_trie restatement -- compact mode, ordered
-key table, fresh prefix strings -- on every core of the process's affinity
-mask over a bounded sample of the same topic stream) and `parity_sample`: the
-last timed step's CSR, still in HBM, compared row for row with the oracle on
-strided windows of the batch (outside the timed region).
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline
+needs and no more: it builds the index, generates the batch, warms up, times
+the N steps and prints the result line.  The line carries the roofline object
+of the dominant kernel (k_match_fused: tokenizer + trie walk, algorithmic bytes
+per SURVEY.md §8d ÷ its HIP-event time): the metric names the achieved HBM GB/s,
+and the kernel times are read from the timed steps themselves.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step
+returned (its CSR: row offsets and sorted ids) as DIR/<name>.npy in float64 --
+every row when the batch is small, a fixed sample of row windows otherwise
+(dump_outputs).  The inputs are seeded, so two builds run with the same
+arguments can be compared array for array.
+
+`--full` adds everything else, outside the timed region: a CPU baseline (the
+oracle's faithful emqx_trie restatement -- compact mode, ordered key table,
+fresh prefix strings -- on every core of the process's affinity mask over a
+bounded sample of the same topic stream), `parity_sample` (the last timed
+step's CSR, still in HBM, compared row for row with the oracle on strided
+windows of the batch), the host-buffer (PCIe-inclusive) call, incremental index
+and subscriber updates, the multi-device context and, at N>1, the ranks' build
+statistics and the replicas' agreement.  The `--no-*` switches trim a --full run.
 """
 
 from __future__ import annotations
@@ -52,6 +66,13 @@ def parse():
     p.add_argument("--filters", type=int, default=None)
     p.add_argument("--topics", type=int, default=None, help="topics per GPU per step")
     p.add_argument("--seed", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline does not need, outside the timed region: CPU baseline, oracle "
+                        "parity sample, host-buffer call, index and subscriber updates, multi-device context, "
+                        "N>1 build statistics (the --no-* switches below trim such a run)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the last timed step's result (rank 0's CSR) as DIR/<name>.npy "
+                        "(float64; a fixed sample of row windows when the batch is large)")
     p.add_argument("--cpu-seconds", type=float, default=15.0)
     p.add_argument("--cpu-threads", type=int, default=None)
     p.add_argument("--no-cpu", action="store_true")
@@ -85,6 +106,13 @@ def parse():
                    help="skip the host-buffer call (PCIe-inclusive rate, reported in detail, never `value`)")
     a = p.parse_args()
     a.no_pipeline = a.no_pipeline or bool(os.environ.get("GM_BENCH_NO_PIPELINE"))  # (A/B scripts set env knobs)
+    if not a.full:  # a plain run: the headline alone
+        asked = [o for o in ("--subs-update", "--replicas", "--cpu-seconds", "--cpu-threads")
+                 if any(x == o or x.startswith(o + "=") for x in sys.argv[1:])]
+        if asked:  # (options that ask for more than the headline)
+            print(f"[bench] {', '.join(asked)}: no effect without --full", file=sys.stderr, flush=True)
+        a.no_cpu = a.no_parity = a.no_update = a.no_multi = a.no_host_io = True
+        a.subs_update = False
     if a.traffic_json is None:
         a.traffic_json = os.path.join(ROOT, "profiles", "traffic.json" if a.config == "c2" else
                                       f"traffic_{a.config}.json")
@@ -447,6 +475,76 @@ def ctypes_ptr(p) -> int:
     return ctypes.cast(p, ctypes.c_void_p).value or 0
 
 
+DUMP_WINDOWS, DUMP_WINDOW_ROWS = 64, 16_384  # the row sample of a large result: 2^20 rows (3 x 8 MB as float64)
+DUMP_MAX_IDS = 4_500_000  # ids written at most (36 MB as float64): the files stay under 64 MB in all
+
+
+def dump_outputs(ctx, res, out_dir, seed, base=0):
+    """`--dump-outputs`: the result of the last timed step (a DeviceCsr still in
+    HBM, or a host (row_off, ids) pair) as float64 .npy files in out_dir:
+
+      shape.npy      [n_rows, nnz] of the whole result
+      rows.npy       the indices of the rows written
+      row_begin.npy  row_off[r] of each such row  } as the caller received them
+      row_end.npy    row_off[r + 1]               } (offsets into the whole ids)
+      ids.npy        the ids of those rows, in row order
+
+    Every row when there are at most DUMP_WINDOWS * DUMP_WINDOW_ROWS of them;
+    otherwise DUMP_WINDOWS aligned windows of DUMP_WINDOW_ROWS rows drawn by a
+    generator seeded with `seed` (the same rows for the same arguments).  ids
+    stop after DUMP_MAX_IDS (C4's rows are 1M wide): ids.npy then holds a prefix
+    of the written rows' ids, its length saying how far it got.  `base`: the
+    offset at which this result's ids start (a C4 part holds the deliveries
+    from `base` on, its row offsets being global)."""
+    import numpy as np
+    if isinstance(res, tuple):
+        hro, hids = res
+        n_rows, nnz, held = len(hro) - 1, int(hro[-1]), len(hids)
+
+        def offsets(s, count):
+            return np.asarray(hro[s:s + count + 1], np.uint64)
+
+        def ids_at(first, count):
+            return np.asarray(hids[first:first + count], np.uint32)
+    else:
+        n_rows, nnz = res.n_rows, res.nnz
+        held = nnz
+        ro_ptr, ids_ptr = ctypes_ptr(res.csr.row_off), ctypes_ptr(res.csr.ids)
+
+        def offsets(s, count):
+            ro = np.zeros(count + 1, np.uint64)
+            ctx.memcpy_d2h(ro, ro_ptr + 8 * s, (count + 1) * 8)
+            return ro
+
+        def ids_at(first, count):
+            ids = np.zeros(max(count, 1), np.uint32)
+            if count:
+                ctx.memcpy_d2h(ids, ids_ptr + 4 * first, count * 4)
+            return ids[:count]
+    width = DUMP_WINDOW_ROWS
+    if n_rows <= DUMP_WINDOWS * width:
+        windows = [(0, n_rows)]
+    else:
+        rng = np.random.default_rng(seed)
+        windows = [(int(b) * width, width) for b in sorted(rng.choice(n_rows // width, DUMP_WINDOWS, replace=False))]
+    rows, begin, end, ids, room = [], [], [], [], DUMP_MAX_IDS
+    for s, count in windows:
+        ro = offsets(s, count)
+        rows.append(np.arange(s, s + count, dtype=np.float64))
+        begin.append(ro[:-1].astype(np.float64))
+        end.append(ro[1:].astype(np.float64))
+        # the window's ids, clipped to the ids this result holds ([base, base + held) of the offsets)
+        lo = min(max(int(ro[0]) - base, 0), held)
+        take = min(max(int(ro[-1]) - base, lo) - lo, held - lo, room)
+        ids.append(ids_at(lo, take).astype(np.float64))
+        room -= take
+    os.makedirs(out_dir, exist_ok=True)
+    empty = [np.zeros(0, np.float64)]
+    for name, parts in (("rows", rows), ("row_begin", begin), ("row_end", end), ("ids", ids)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.concatenate(parts + empty))
+    np.save(os.path.join(out_dir, "shape.npy"), np.array([n_rows, nnz], np.float64))
+
+
 def heartbeat(every_s: float = 60.0):
     """A line on stderr every minute while the bench runs (the 100M-filter C5
     index alone builds for ~2.5 min in one library call)."""
@@ -799,7 +897,7 @@ def main():
         ust = ctx.update_stats()
         build_info.update(index_import_mirror_loaded=ust["mirror_loaded"],
                           index_import_mirror_bytes=ust["mirror_bytes"], index_import_mirror_ms=ust["mirror_ms"])
-    if pg is not None:  # how many ranks compiled, the slowest rank's build, the largest host RSS
+    if pg is not None and a.full:  # how many ranks compiled, the slowest rank's build, the largest host RSS
         n_built = _reduce_tensor(local, float(source == "built"))
         pg.all_reduce(n_built)
         build_info.update(ranks_compiled=int(n_built.item()), index_build_s_max=barrier_max(pg, local, t_build),
@@ -851,6 +949,8 @@ def main():
     barrier(pg)
     elapsed = time.perf_counter() - t0
     elapsed = barrier_max(pg, local, elapsed)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(ctx, last, a.dump_outputs, a.seed)
 
     ms_per_step = elapsed * 1000.0 / a.steps
     value = world * n_topics * a.steps / elapsed
@@ -1040,6 +1140,8 @@ def bench_c5(a, world, rank, local, pg):
     ctx.synchronize()
     barrier(pg)
     elapsed = barrier_max(pg, local, time.perf_counter() - t0)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(ctx, res, a.dump_outputs, a.seed)
     if pg is not None:
         t = _reduce_tensor(local, float(nnz))
         pg.all_reduce(t)
@@ -1122,6 +1224,8 @@ def bench_c5_prefix(a, world, rank, local, pg):
     ctx.synchronize()
     barrier(pg)
     elapsed = barrier_max(pg, local, time.perf_counter() - t0)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(ctx, last, a.dump_outputs, a.seed)
     walked = [m.last_topics_walked]
     if pg is not None:
         import torch
@@ -1195,14 +1299,19 @@ def bench_c4(a, world, rank, local, pg):
     kms = []
     t0 = time.perf_counter()
     part = 0
-    for _ in range(a.steps):
+    keep = a.steps - 1 if a.dump_outputs and rank == 0 else -1  # (--dump-outputs: the last step's part is kept)
+    for i in range(a.steps):
         r, first = ctx.fanout_part(idx, m, rank, world)
         part = r.nnz
         kms.append(ctx.stats()["match_kernel_ms"])
-        r.free()
+        if i != keep:
+            r.free()
     ctx.synchronize()
     barrier(pg)
     elapsed = barrier_max(pg, local, time.perf_counter() - t0)
+    if keep >= 0:
+        dump_outputs(ctx, r, a.dump_outputs, a.seed, base=first)
+        r.free()
     parts = [part]
     if pg is not None:
         import torch

@@ -20,8 +20,8 @@ if [ "$MODE" = all ] || [ "$MODE" = test ]; then
   step smoke 180 python -u -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-  step bench_small 300 python -u bench.py --topics 10000000 --steps 3 --warmup 1 --cpu-seconds 5
-  step bench 600 python -u bench.py
+  step bench_small 300 python -u bench.py --full --topics 10000000 --steps 3 --warmup 1 --cpu-seconds 5
+  step bench 600 python -u bench.py --full
 fi
 if [ "$MODE" = prof ]; then
   cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
