@@ -64,8 +64,8 @@ class UpdateStats(C.Structure):
                 ("blobs_reused", C.c_uint32), ("blobs_fresh", C.c_uint32)]
 
 
-UPD_KINDS = {0: "none", 1: "patch", 2: "overlay", 3: "rebuild", 4: "subs_only", 5: "build", 6: "import"}
-REP_MODES = {0: "none", 1: "patched", 2: "copied", 3: "shared"}
+UPD_KINDS = {0: "none", 1: "patch", 2: "overlay", 3: "rebuild", 4: "subs_only", 5: "build", 6: "import", 7: "shift"}
+REP_MODES = {0: "none", 1: "patched", 2: "copied", 3: "shared", 4: "sharded"}
 
 
 # Every symbol declared in include/emqx_gpu_match.h and include/emqx_gm_ext.h.
@@ -127,6 +127,8 @@ SIGNATURES = {
     "emqx_gm_select_filters": (_i32, [_vp, _vp, _u64, _vp, _u32, _vp, _vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "emqx_gm_last_update_stats": (_i32, [_vp, C.POINTER(UpdateStats)]),
     "emqx_gm_index_replica_digest": (_i32, [_vp, _vp, _u32, C.POINTER(_u64), C.POINTER(_u64)]),
+    "emqx_gm_last_shard_update": (_i32, [_vp, _vp, C.POINTER(_u32)]),
+    "emqx_gm_route_filter_shards_host": (_i32, [_vp, _vp, _vp, _u64, _vp]),
 }
 
 _LIB = None

@@ -501,11 +501,14 @@ int emqx_gm_index_update(emqx_gm_ctx* ctx, emqx_gm_index* prev, const uint8_t* f
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   if (prev && prev->device != ctx->device)
     return gm::set_err(ctx, EMQX_GM_EINVAL, "index_update: index lives on another device");
-  if (prev && prev->route)
-    return gm::set_err(ctx, EMQX_GM_EUNSUPPORTED, "index_update: sharded index (rebuild it)");
   GM_GUARD_BEGIN
   const double t0 = begin_index_call(EMQX_GM_UPD_NONE);
   hipSetDevice(ctx->device);
+  if (prev && prev->route) {  // a sharded index: every shard applies its share at once (gm_shard.cpp)
+    const int rc = gm::update_sharded(ctx, prev, fb, fo, ops, n_ops, out);
+    gm::tl_ustats.total_ms = gm::now_ms() - t0;
+    return rc;
+  }
   return replicated(ctx, gm::update_index(ctx, prev, fb, fo, ops, n_ops, out), prev, out, t0);
   GM_GUARD_END(ctx)
 }
@@ -749,7 +752,7 @@ int emqx_gm_fanout(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_csr
   if (idx->route) {  // a sharded index: each row on the shard of its filters (gm_shard.cpp)
     if ((flags & EMQX_GM_DEVICE_IO) || m->on_device)
       return gm::set_err(ctx, EMQX_GM_EUNSUPPORTED, "fanout: sharded index takes host rows");
-    if (idx->subs.empty()) return gm::set_err(ctx, EMQX_GM_EINVAL, "fanout: index without subscriber lists");
+    // (built without subscriber lists -- the updatable form: no deliveries, as a plain index gives)
     return noted(ctx, ctx, gm::run_fanout_sharded(ctx, idx, m, flags, out));
   }
   if (!ctx->members.empty() && !(flags & EMQX_GM_DEVICE_IO) && !m->on_device)
@@ -856,6 +859,15 @@ int emqx_gm_last_stats(const emqx_gm_ctx* ctx, emqx_gm_match_stats* stats) {
 int emqx_gm_last_update_stats(const emqx_gm_ctx* ctx, emqx_gm_update_stats* stats) {
   if (!ctx || !stats) return EMQX_GM_EINVAL;
   *stats = gm::tl_ustats;
+  return EMQX_GM_OK;
+}
+
+int emqx_gm_last_shard_update(const emqx_gm_ctx* ctx, uint32_t* kinds, uint32_t* n) {
+  if (!ctx || !n) return EMQX_GM_EINVAL;
+  const std::vector<uint32_t>& k = gm::last_shard_kinds();
+  if (kinds)
+    for (uint32_t i = 0; i < *n && i < k.size(); ++i) kinds[i] = k[i];
+  *n = uint32_t(k.size());
   return EMQX_GM_OK;
 }
 
@@ -1012,6 +1024,12 @@ int emqx_gm_route_topics_host(const emqx_gm_route* route, const uint8_t* tb, con
                               uint32_t* dest) {
   if (!route || (n && (!tb || !to || !dest))) return EMQX_GM_EINVAL;
   return gm::route_topics_host(route, tb, to, n, dest);
+}
+
+int emqx_gm_route_filter_shards_host(const emqx_gm_route* route, const uint8_t* fb, const uint64_t* fo, uint64_t n,
+                                     uint32_t* shard_out) {
+  if (!route || (n && (!fb || !fo || !shard_out))) return EMQX_GM_EINVAL;
+  return gm::route_filter_shards_host(route, fb, fo, n, shard_out);
 }
 
 int emqx_gm_route_topics(emqx_gm_ctx* ctx, emqx_gm_route* route, const uint8_t* d_tb, const uint64_t* d_to, uint64_t n,

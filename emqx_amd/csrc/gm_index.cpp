@@ -289,7 +289,7 @@ void sort_filters(std::vector<uint32_t>& ord, const uint8_t* fb, const uint64_t*
 
 int build_index(emqx_gm_ctx* ctx, const uint8_t* fb, const uint64_t* fo, uint64_t n, const uint64_t* sub_off,
                 const uint32_t* sub_ids, uint32_t* perm_out, emqx_gm_index** out, emqx_gm_index_info_t* host_only,
-                const uint32_t* gids) {
+                const uint32_t* gids, bool shard_mirror) {
   if (!out && !host_only) return set_err(ctx, EMQX_GM_EINVAL, "index_build: out is NULL");
   if (n && (!fb || !fo)) return set_err(ctx, EMQX_GM_EINVAL, "index_build: NULL filter buffers");
   if (n >= 0x7FFFFFFFull) return set_err(ctx, EMQX_GM_EINVAL, "index_build: too many filters");
@@ -1370,7 +1370,9 @@ int build_index(emqx_gm_ctx* ctx, const uint8_t* fb, const uint64_t* fo, uint64_
   // keep_mirror: the layout reserves update headroom and the index carries a
   // Mirror; its host copy of the blob is kept from here (eager) or downloaded
   // on the line's first update (load_mirror_blob), see EMQX_GM_OPEN_MIRROR_*
-  const bool keep_mirror = host_mirror || (ctx && !gids && !knob("GM_NO_MIRROR"));
+  // (a shard of emqx_gm_index_build_sharded without subscriber lists too: the
+  // sharded update patches it; a stand-alone shard index stays as it was)
+  const bool keep_mirror = host_mirror || (ctx && (!gids || (shard_mirror && !sub_off)) && !knob("GM_NO_MIRROR"));
   const uint64_t nodes_cap = keep_mirror ? NN + NN / 4 + 1024 : NN;
   const uint64_t arena_cap = keep_mirror ? arena.size() + arena.size() / 4 + 65536 : arena.size();
   const uint64_t flen_cap = keep_mirror ? uint64_t(nf) + nf / 4 + 1024 : nf;
@@ -1660,6 +1662,10 @@ void free_index(emqx_gm_index* idx) {
     (void)hipSetDevice(idx->device);
     if (idx->dev_base && !idx->blob_owner) give_spare_blob(idx->device, idx->dev_base, idx->dev_bytes);
     if (idx->dev_subs) (void)hipFree(idx->dev_subs);
+  }
+  if (idx->dev_gmap) {
+    (void)hipSetDevice(idx->device);
+    (void)hipFree(idx->dev_gmap);
   }
   if (idx->blob_owner && idx->blob_owner->refs.fetch_sub(1) == 1) free_index(idx->blob_owner);
   delete idx;

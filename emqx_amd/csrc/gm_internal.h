@@ -281,6 +281,7 @@ struct emqx_gm_index {
   void* dev_subs = nullptr;     // a subscriber CSR of its own (after emqx_gm_index_update_subs), or nullptr
   size_t subs_bytes = 0;        // ... its bytes
   emqx_gm_index* blob_owner = nullptr;  // set: dev_base is that (retained) snapshot's blob, shared
+  void* dev_gmap = nullptr;     // a shard's id map of its own (after a sharded update, gm_shard.cpp): view.gmap, or nullptr
   size_t dev_bytes = 0;
   gm::IndexView view{};
   uint16_t* dev_flen = nullptr; // filter lengths (stats only), inside dev_base
@@ -315,7 +316,8 @@ namespace gm {
 // gm_index.cpp
 int build_index(emqx_gm_ctx* ctx, const uint8_t* fb, const uint64_t* fo, uint64_t n, const uint64_t* sub_off,
                 const uint32_t* sub_ids, uint32_t* perm_out, emqx_gm_index** out,
-                emqx_gm_index_info_t* host_only = nullptr, const uint32_t* gids = nullptr);
+                emqx_gm_index_info_t* host_only = nullptr, const uint32_t* gids = nullptr,
+                bool shard_mirror = false);  // shard_mirror: a shard index (gids) built updatable (build_sharded)
 void sort_filters(std::vector<uint32_t>& ord, const uint8_t* fb, const uint64_t* fo);
 void free_index(emqx_gm_index* idx);
 // gm_index.cpp: a freed snapshot's device blob kept, one per device, for the
@@ -364,7 +366,13 @@ int route_topics_device(emqx_gm_ctx* ctx, emqx_gm_route* r, const uint8_t* d_tb,
                         uint32_t* d_dest);
 int route_partition(emqx_gm_ctx* ctx, emqx_gm_route* r, const uint8_t* d_tb, const uint64_t* d_to, uint64_t n,
                     uint32_t* d_perm, uint32_t* d_plen, uint64_t* d_split);
-void free_route(emqx_gm_route* r);
+void free_route(emqx_gm_route* r);  // drops one reference
+void retain_route(emqx_gm_route* r);
+uint32_t route_n_shards(const emqx_gm_route* r);
+// the shard of a filter under a fixed route (EMQX_GM_ALL_SHARDS: every one), gm_route.hip
+uint32_t route_filter_shard(const emqx_gm_route* r, const uint8_t* f, uint64_t len);
+int route_filter_shards_host(const emqx_gm_route* r, const uint8_t* fb, const uint64_t* fo, uint64_t n,
+                             uint32_t* shard_out);
 int permute_topics(emqx_gm_ctx* ctx, const uint8_t* d_tb, const uint64_t* d_to, uint64_t n, const uint32_t* d_perm,
                    uint8_t* d_out, uint64_t* d_out_off);
 int unpermute_rows(emqx_gm_ctx* ctx, uint64_t n, const uint32_t* d_perm, const uint32_t* d_lens, const uint32_t* d_ids,
@@ -410,9 +418,12 @@ int update_index(emqx_gm_ctx* ctx, emqx_gm_index* prev, const uint8_t* fb, const
 // trie_only: the new blob holds the tables up to the subscriber CSR only (the
 // caller gives the snapshot a CSR of its own).
 // reps (optional): the member replicas to patch alongside (RepTarget::out set on success).
+// gs (optional, a shard of a sharded index): the new snapshot gets an id map
+// of its own (dev_gmap), written in the same device step.
+struct GmapShift;
 int patch_update(emqx_gm_ctx* ctx, emqx_gm_index* prev, const std::set<uint32_t>& tomb,
                  const std::set<std::string>& dset, emqx_gm_index** out, std::vector<uint32_t>* rmap_out = nullptr,
-                 bool trie_only = false, std::vector<RepTarget>* reps = nullptr);
+                 bool trie_only = false, std::vector<RepTarget>* reps = nullptr, const GmapShift* gs = nullptr);
 bool well_formed_filter(const uint8_t* p, uint64_t len);
 // gm_image.cpp: index images (emqx_gm_index_export / _import) and the lazy host mirror
 int index_export(emqx_gm_ctx* ctx, const emqx_gm_index* idx, uint32_t flags, uint8_t* buf, uint64_t* size);
@@ -479,6 +490,35 @@ int apply_patch_device(emqx_gm_ctx* ctx, void* dst, const void* src, size_t byte
                        const std::vector<std::pair<uint64_t, uint32_t>>& ranges, const uint8_t* host,
                        const IndexView& v, uint64_t o_hot, uint64_t o_nodes, uint64_t n_nodes,
                        const IdShift& shift, const std::vector<std::pair<uint64_t, uint32_t>>& orops);
+// ... of a shard of a sharded index: gmap (nullptr: none) is the shard's new id
+// map, queued behind the patch on the same stream (k_gmap_shift reads the
+// shift's device table); one synchronize covers both.
+struct GmapJob;
+int apply_patch_device_gmap(emqx_gm_ctx* ctx, void* dst, const void* src, size_t bytes,
+                            const std::vector<std::pair<uint64_t, uint32_t>>& ranges, const uint8_t* host,
+                            const IndexView& v, uint64_t o_hot, uint64_t o_nodes, uint64_t n_nodes,
+                            const IdShift& shift, const std::vector<std::pair<uint64_t, uint32_t>>& orops,
+                            const GmapJob* gmap);
+// The id change of a sharded update as one shard sees it (gm_shard.cpp): G is
+// the GLOBAL shift (old global id -> new), add_gid the final global ids of the
+// filters this shard gains, in byte order.
+struct GmapShift {
+  const IdShift* G = nullptr;
+  const std::vector<uint32_t>* add_gid = nullptr;
+};
+// gm_match.hip, k_gmap_shift: a shard's new local-to-global id map.  For every
+// old or temporary local id i < nb + add_gid.size(): j = L(i) (rmap on the
+// device, the shard's local shift; nullptr: the identity, no local change;
+// NONE: deleted), new_gmap[j] = G(old_gmap[i]) for i < nb, else add_gid[i - nb].
+struct GmapJob {
+  const uint32_t* old_gmap = nullptr;  // device, nb entries ascending (may be null when nb == 0)
+  uint64_t nb = 0;
+  GmapShift sh;
+  uint32_t* new_gmap = nullptr;  // device, n_new entries
+  uint64_t n_new = 0;
+};
+// a shard without local changes: its new map alone (queued and waited for on ctx's stream)
+int shift_gmap_device(emqx_gm_ctx* ctx, const GmapJob& job);
 // gm_match.hip
 int run_match_overlay(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to, uint64_t n,
                       uint32_t flags, emqx_gm_csr* out);
@@ -561,6 +601,12 @@ int run_match_sharded(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t*
                       uint32_t flags, emqx_gm_csr* out);
 int run_fanout_sharded(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_csr* m, uint32_t flags,
                        emqx_gm_csr* out);
+// emqx_gm_index_update on a sharded index built without subscriber lists: each
+// shard patched, given a new id map only, or rebuilt alone (all at once)
+int update_sharded(emqx_gm_ctx* ctx, emqx_gm_index* prev, const uint8_t* fb, const uint64_t* fo, const uint8_t* ops,
+                   uint64_t n_ops, emqx_gm_index** out);
+// what each shard of the calling thread's last sharded update did (EMQX_GM_UPD_PATCH / _SHIFT / _REBUILD)
+const std::vector<uint32_t>& last_shard_kinds();
 // emqx_gm_fanout of host rows over a multi-device context's replicas (one
 // slice per device, one page-locked result); small batches: run_fanout
 int run_fanout_multi(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_csr* m, uint32_t flags,

@@ -2648,6 +2648,64 @@ __global__ __launch_bounds__(256) void k_shift_table(uint32_t* __restrict__ rmap
   }
   rmap[id] = x - below + count_below(addpos, na, x + 1);  // inserts at or before it
 }
+// A shard's new local-to-global id map after a sharded update (gm_shard.cpp,
+// GmapJob): rows leave the device through view.gmap[local id], and one insert
+// anywhere shifts global ids on every shard.  For every old or temporary local
+// id i < nb + na: j = rmap[i] (the shard's local shift, k_shift_table's table;
+// nullptr: the identity; NONE: deleted), new_gmap[j] = G(old_gmap[i]) for a
+// surviving filter, add_gid[i - nb] for a new one, with G(g) = g - (gdels < g)
+// + (gadds <= g) the GLOBAL shift.  old_gmap ascends, so the 256 elements of a
+// tile bracket a narrow window of gdels / gadds: four lanes find it with full
+// searches on the tile's first and last element, the windows are staged in LDS
+// when they fit, and each lane searches only inside them.  A streaming pass:
+// 4 B read and 4 B written per filter (writes monotone in i).
+constexpr uint32_t GMAP_WIN = 1024;
+__global__ __launch_bounds__(256) void k_gmap_shift(const uint32_t* __restrict__ old_gmap, uint32_t nb, uint32_t na,
+                                                    const uint32_t* __restrict__ rmap,
+                                                    const uint32_t* __restrict__ add_gid,
+                                                    const uint32_t* __restrict__ gdels, uint32_t gnd,
+                                                    const uint32_t* __restrict__ gadds, uint32_t gna,
+                                                    uint32_t* __restrict__ new_gmap, uint32_t n_new) {
+  __shared__ uint32_t s_d[GMAP_WIN], s_a[GMAP_WIN];
+  __shared__ uint32_t s_w[4];  // dels window [0], [1]; adds window [2], [3]
+  const uint64_t n_map = uint64_t(nb) + na;
+  for (uint64_t base = uint64_t(blockIdx.x) * 256u; base < n_map; base += uint64_t(gridDim.x) * 256u) {
+    uint32_t d_lo = 0, d_hi = 0, a_lo = 0, a_hi = 0;
+    bool ld = false, la = false;
+    if (base < nb) {  // (block-uniform) the tile's old ids: [base, hi)
+      const uint32_t hi = uint32_t(min(base + 256u, uint64_t(nb)));
+      if (threadIdx.x < 4) {
+        const uint32_t g = old_gmap[(threadIdx.x & 1) ? hi - 1 : uint32_t(base)];
+        s_w[threadIdx.x] = threadIdx.x < 2 ? count_below(gdels, gnd, g) : count_below(gadds, gna, g + 1);
+      }
+      __syncthreads();
+      d_lo = s_w[0], d_hi = max(s_w[0], s_w[1]), a_lo = s_w[2], a_hi = max(s_w[2], s_w[3]);
+      ld = d_hi - d_lo <= GMAP_WIN;
+      la = a_hi - a_lo <= GMAP_WIN;
+      if (ld)
+        for (uint32_t k = threadIdx.x; k < d_hi - d_lo; k += 256) s_d[k] = gdels[d_lo + k];
+      if (la)
+        for (uint32_t k = threadIdx.x; k < a_hi - a_lo; k += 256) s_a[k] = gadds[a_lo + k];
+      __syncthreads();
+    }
+    const uint64_t i = base + threadIdx.x;
+    if (i < n_map) {
+      const uint32_t j = rmap ? rmap[i] : uint32_t(i);
+      if (j != NONE && j < n_new) {
+        if (i >= nb) {
+          new_gmap[j] = add_gid[i - nb];
+        } else {
+          const uint32_t g = old_gmap[i];
+          const uint32_t below = d_lo + (ld ? count_below(s_d, d_hi - d_lo, g) : count_below(gdels + d_lo, d_hi - d_lo, g));
+          const uint32_t ins =
+              a_lo + (la ? count_below(s_a, a_hi - a_lo, g + 1) : count_below(gadds + a_lo, a_hi - a_lo, g + 1));
+          new_gmap[j] = g - below + ins;
+        }
+      }
+    }
+    __syncthreads();  // (the next tile restages the windows)
+  }
+}
 // Flag bits set on words whose other bits are filter ids (HOT_PLUS on hf /
 // p_hf): the host mirror's ids are stale (not renumbered), so these go as ORs.
 __global__ __launch_bounds__(256) void k_patch_or(uint32_t* __restrict__ dst, const uint64_t* __restrict__ ops,
@@ -2739,10 +2797,57 @@ bool renum_payload(uint8_t* buf, uint64_t a, uint64_t b, uint64_t o, uint64_t n,
 }
 }  // namespace
 
+namespace {
+// k_gmap_shift queued on ctx's stream: the global shift's lists and the new
+// filters' ids go up in one copy (stage / dbuf: kept by the caller until it has
+// synchronized the stream); rmap: the local shift's device table (n_map
+// entries), or nullptr for a shard without local changes.
+int queue_gmap_shift(emqx_gm_ctx* ctx, const GmapJob& job, const uint32_t* rmap, uint64_t n_map,
+                     std::vector<uint32_t>& stage, PoolBuf& dbuf) {
+  const IdShift& G = *job.sh.G;
+  const std::vector<uint32_t>& ag = *job.sh.add_gid;
+  const uint64_t gnd = G.dels.size(), gna = G.addpos.size(), na = ag.size();
+  if (job.nb + na != n_map || (!rmap && na) || (job.nb && !job.old_gmap) || !job.new_gmap ||
+      job.nb + na >= 0xFFFFFFFFull || G.nb + gna >= 0xFFFFFFFFull)
+    return set_err(ctx, EMQX_GM_EINVAL, "index_update: id map job");
+  if (!n_map) return EMQX_GM_OK;
+  stage.resize(gnd + gna + na + 1);
+  for (uint64_t k = 0; k < gnd; ++k) stage[k] = uint32_t(G.dels[k]);
+  for (uint64_t k = 0; k < gna; ++k) stage[gnd + k] = uint32_t(G.addpos[k]);
+  for (uint64_t k = 0; k < na; ++k) stage[gnd + gna + k] = ag[k];
+  dbuf = PoolBuf(ctx->pool, stage.size() * 4);
+  if (!dbuf.p) return set_err(ctx, EMQX_GM_ENOMEM, "index_update: id map staging");
+  hipStream_t s = ctx->stream;
+  GM_HIP(ctx, hipMemcpyAsync(dbuf.p, stage.data(), stage.size() * 4, hipMemcpyHostToDevice, s));
+  const uint32_t* D = dbuf.as<uint32_t>();
+  const uint64_t g = std::min<uint64_t>(4096, (n_map + 255) / 256);
+  hipLaunchKernelGGL(k_gmap_shift, dim3(uint32_t(g)), dim3(256), 0, s, job.old_gmap, uint32_t(job.nb), uint32_t(na),
+                     rmap, D + gnd + gna, D, uint32_t(gnd), D + gnd, uint32_t(gna), job.new_gmap, uint32_t(job.n_new));
+  GM_HIP(ctx, hipGetLastError());
+  return EMQX_GM_OK;
+}
+}  // namespace
+
+int shift_gmap_device(emqx_gm_ctx* ctx, const GmapJob& job) {
+  std::vector<uint32_t> stage;
+  PoolBuf dbuf;
+  if (const int rc = queue_gmap_shift(ctx, job, nullptr, job.nb, stage, dbuf)) return rc;
+  GM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return EMQX_GM_OK;
+}
+
 int apply_patch_device(emqx_gm_ctx* ctx, void* dst, const void* src, size_t bytes,
                        const std::vector<std::pair<uint64_t, uint32_t>>& ranges, const uint8_t* host,
                        const IndexView& v, uint64_t o_hot, uint64_t o_nodes, uint64_t n_nodes,
                        const IdShift& shift, const std::vector<std::pair<uint64_t, uint32_t>>& orops) {
+  return apply_patch_device_gmap(ctx, dst, src, bytes, ranges, host, v, o_hot, o_nodes, n_nodes, shift, orops, nullptr);
+}
+
+int apply_patch_device_gmap(emqx_gm_ctx* ctx, void* dst, const void* src, size_t bytes,
+                            const std::vector<std::pair<uint64_t, uint32_t>>& ranges, const uint8_t* host,
+                            const IndexView& v, uint64_t o_hot, uint64_t o_nodes, uint64_t n_nodes,
+                            const IdShift& shift, const std::vector<std::pair<uint64_t, uint32_t>>& orops,
+                            const GmapJob* gmap) {
   uint64_t n_hot = 0;
   for (int t = 0; t < HOT_TABLES; ++t) n_hot = std::max<uint64_t>(n_hot, v.hot_off[t] + v.hot_cap[t]);
   const uint64_t hot_end = o_hot + n_hot * sizeof(HotSlot), nodes_end = o_nodes + n_nodes * sizeof(Node);
@@ -2860,6 +2965,14 @@ int apply_patch_device(emqx_gm_ctx* ctx, void* dst, const void* src, size_t byte
                        n_hot, reinterpret_cast<Node*>(D + o_nodes), n_nodes, RM);
     GM_HIP(ctx, hipGetLastError());
   }
+  // a shard's new id map, behind the patch on the same stream (it reads the shift's table)
+  std::vector<uint32_t> gm_stage;
+  PoolBuf gm_dbuf;
+  if (gmap)
+    if (const int rc = queue_gmap_shift(ctx, *gmap, RM, n_map, gm_stage, gm_dbuf)) {
+      (void)hipStreamSynchronize(s);
+      return rc;
+    }
   GM_HIP(ctx, hipStreamSynchronize(s));  // the staging buffers go back to the pool / the host
   return EMQX_GM_OK;
 }

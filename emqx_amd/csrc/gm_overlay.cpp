@@ -489,6 +489,15 @@ void renumber_host(Mirror& M, const IndexView& v, const std::vector<uint32_t>& r
 
 }  // namespace
 
+// (the device build defines it in gm_match.hip; the host-only ASAN build of
+// this file links this stand-in: no shard index is patched without a device)
+__attribute__((weak)) int apply_patch_device_gmap(emqx_gm_ctx* ctx, void*, const void*, size_t,
+                                                  const std::vector<std::pair<uint64_t, uint32_t>>&, const uint8_t*,
+                                                  const IndexView&, uint64_t, uint64_t, uint64_t, const IdShift&,
+                                                  const std::vector<std::pair<uint64_t, uint32_t>>&, const GmapJob*) {
+  return set_err(ctx, EMQX_GM_EDEVICE, "index_update: no device step in this build");
+}
+
 bool well_formed_filter(const uint8_t* p, uint64_t len) { return well_formed(p, len); }
 uint64_t filter_rank(const emqx_gm_index* idx, const uint8_t* f, uint64_t len, bool* found) {
   return base_rank(idx, f, len, found);
@@ -497,7 +506,7 @@ uint64_t filter_rank(const emqx_gm_index* idx, const uint8_t* f, uint64_t len, b
 // Returns 1 (nothing changed) when the snapshot's tables lack room: the caller rebuilds.
 int patch_update(emqx_gm_ctx* ctx, emqx_gm_index* prev, const std::set<uint32_t>& tomb,
                  const std::set<std::string>& dset, emqx_gm_index** out, std::vector<uint32_t>* rmap_out,
-                 bool trie_only, std::vector<RepTarget>* reps) {
+                 bool trie_only, std::vector<RepTarget>* reps, const GmapShift* gs) {
   if (const int rc = load_mirror_blob(ctx, prev)) return rc;  // (a lazy mirror: the first update loads it)
   Mirror& M = *prev->mirror;
   const uint64_t nb = prev->info.n_filters, K = dset.size();
@@ -588,8 +597,23 @@ int patch_update(emqx_gm_ctx* ctx, emqx_gm_index* prev, const std::set<uint32_t>
       }
     }
     dst->dev_bytes = blob_bytes;
-    if (const int rc = apply_patch_device(c, dst->dev_base, src->dev_base, blob_bytes, P.dirty, M.blob.data(), v,
-                                          M.o_hot, M.o_nodes, M.nodes_n, shift, P.orops))
+    GmapJob gj;
+    if (gs) {  // a shard of a sharded index: an id map of its own, written in the same device step
+      const hipError_t e = hipMalloc(&dst->dev_gmap, (nf_new + 1) * 4);
+      if (e != hipSuccess) {
+        dst->dev_gmap = nullptr;
+        return set_err(c, EMQX_GM_ENOMEM, std::string("index_update: hipMalloc (id map): ") + hipGetErrorString(e));
+      }
+      gj.old_gmap = src->view.gmap;
+      gj.nb = nb;
+      gj.sh = *gs;
+      gj.new_gmap = static_cast<uint32_t*>(dst->dev_gmap);
+      gj.n_new = nf_new;
+    }
+    if (const int rc = gs ? apply_patch_device_gmap(c, dst->dev_base, src->dev_base, blob_bytes, P.dirty,
+                                                    M.blob.data(), v, M.o_hot, M.o_nodes, M.nodes_n, shift, P.orops, &gj)
+                          : apply_patch_device(c, dst->dev_base, src->dev_base, blob_bytes, P.dirty, M.blob.data(), v,
+                                               M.o_hot, M.o_nodes, M.nodes_n, shift, P.orops))
       return rc;
     // the view's pointers follow the new blob
     IndexView w = v;
@@ -607,6 +631,7 @@ int patch_update(emqx_gm_ctx* ctx, emqx_gm_index* prev, const std::set<uint32_t>
     w.sub_ids = trie_only ? nullptr : rebase(w.sub_ids);
     w.efilt = rebase(w.efilt);
     w.mph_word = rebase(w.mph_word);
+    if (gs) w.gmap = static_cast<const uint32_t*>(dst->dev_gmap);  // (not the previous blob's)
     dst->dev_flen = reinterpret_cast<uint16_t*>(NB + M.o_flen);
     if (w.flags & IX_D0) {  // the root's '+' record again, from the patched and renumbered tables
       const int rc = refresh_d0(c, w, const_cast<uint32_t*>(w.d0_root));

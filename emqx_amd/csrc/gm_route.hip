@@ -45,6 +45,7 @@ struct RouteSlot {
 }  // namespace gm
 
 struct emqx_gm_route {
+  std::atomic<int> refs{1};  // the snapshots of one sharded line share it (free_route drops one)
   uint32_t n_shards = 1;
   std::vector<gm::RouteSlot> slots;  // open addressing, power-of-two capacity
   std::vector<uint8_t> arena;        // key bytes ('w' or 'w/v')
@@ -387,6 +388,47 @@ int route_topics_host(const emqx_gm_route* r, const uint8_t* tb, const uint64_t*
   return EMQX_GM_OK;
 }
 
+// The shard of a filter under the route as it stands (no re-plan, no newly
+// split word): every shard for a filter any topic of several shards may match
+// ('+' / '#' first; under a split first word the word alone or a '+' / '#'
+// second word), else the shard rt_route gives the filter's own bytes read as a
+// topic -- the one every topic able to match it is routed to, and for a filter
+// the plan was made from, its shard_out.
+uint32_t route_filter_shard(const emqx_gm_route* r, const uint8_t* f, uint64_t len) {
+  const uint32_t mask = uint32_t(r->slots.size() - 1);
+  uint64_t e0 = 0;
+  while (e0 < len && f[e0] != '/') ++e0;
+  auto wild = [&](uint64_t a, uint64_t b) { return b - a == 1 && (f[a] == '+' || f[a] == '#'); };
+  if (wild(0, e0)) return EMQX_GM_ALL_SHARDS;
+  const uint32_t h = rt_hash(f, uint32_t(e0));
+  for (uint32_t s = h & mask;; s = (s + 1) & mask) {  // is the first word split?
+    const RouteSlot& q = r->slots[s];
+    if (q.len == RT_EMPTY) break;
+    if (q.hash == h && q.len == e0 && std::memcmp(r->arena.data() + q.off, f, e0) == 0) {
+      if (q.shard & RT_SPLIT) {
+        if (e0 == len) return EMQX_GM_ALL_SHARDS;
+        uint64_t e1 = e0 + 1;
+        while (e1 < len && f[e1] != '/') ++e1;
+        if (wild(e0 + 1, e1)) return EMQX_GM_ALL_SHARDS;
+      }
+      break;
+    }
+  }
+  return rt_route(r->slots.data(), mask, r->arena.data(), r->n_shards, f, uint32_t(len));
+}
+
+int route_filter_shards_host(const emqx_gm_route* r, const uint8_t* fb, const uint64_t* fo, uint64_t n,
+                             uint32_t* shard_out) {
+  for (uint64_t i = 0; i < n; ++i) {
+    if (fo[i + 1] < fo[i] || fo[i + 1] - fo[i] >= (1ull << 31)) return EMQX_GM_EINVAL;
+    shard_out[i] = route_filter_shard(r, fb + fo[i], fo[i + 1] - fo[i]);
+  }
+  return EMQX_GM_OK;
+}
+
+void retain_route(emqx_gm_route* r) { r->refs.fetch_add(1); }
+uint32_t route_n_shards(const emqx_gm_route* r) { return r->n_shards; }
+
 int route_topics_device(emqx_gm_ctx* ctx, emqx_gm_route* r, const uint8_t* d_tb, const uint64_t* d_to, uint64_t n,
                         uint32_t* d_dest) {
   void* dev = nullptr;
@@ -447,6 +489,7 @@ int route_partition(emqx_gm_ctx* ctx, emqx_gm_route* r, const uint8_t* d_tb, con
 }
 
 void free_route(emqx_gm_route* r) {
+  if (r->refs.fetch_sub(1) != 1) return;
   for (auto& kv : r->dev) {
     hipSetDevice(kv.first);
     hipFree(kv.second);

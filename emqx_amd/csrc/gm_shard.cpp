@@ -22,13 +22,22 @@
 //   fan-out host rows: each row goes to the shard of its filters (all on the
 //           row's topic's shard, or on every shard), its global ids mapped to
 //           that shard's local ones, fanned out there, and put back in order.
-// Updates, images and device-buffer calls on a sharded index are refused
-// (EMQX_GM_EUNSUPPORTED): a global id shifts on every shard when any filter
-// is added, so a sharded set is rebuilt.
+//   update  (an index built without subscriber lists) the route of a snapshot
+//           line is fixed: a new filter goes to the shard its matching topics
+//           are routed to (route_filter_shard), a shard with local changes is
+//           patched in place like a plain index, and EVERY shard gets a new
+//           local-to-global id map from one device pass (k_gmap_shift) -- a
+//           global id shifts on every shard when any filter is added; a shard
+//           that cannot be patched is rebuilt alone (update_sharded).
+// Images, device-buffer calls, emqx_gm_index_update_subs and updates of a
+// sharded index built with subscriber lists are refused
+// (EMQX_GM_EUNSUPPORTED): such a set is rebuilt.
 #include <algorithm>
 #include <cstring>
 #include <memory>
 #include <numeric>
+#include <set>
+#include <string>
 #include <thread>
 
 #include "gm_internal.h"
@@ -142,7 +151,7 @@ int build_sharded(emqx_gm_ctx* ctx, const uint8_t* fb, const uint64_t* fo, uint6
     if (si.empty()) si.push_back(0);
     std::vector<uint32_t> perm(g.size() + 1);
     return build_index(mem[k], b.data(), o.data(), g.size(), sub_off ? so.data() : nullptr, sub_off ? si.data() : nullptr,
-                       perm.data(), &idx->shards[k], nullptr, g.empty() ? nullptr : g.data());
+                       perm.data(), &idx->shards[k], nullptr, g.empty() ? nullptr : g.data(), true);
   });
   hipSetDevice(ctx->device);
   if (rc) {
@@ -169,6 +178,351 @@ int build_sharded(emqx_gm_ctx* ctx, const uint8_t* fb, const uint64_t* fo, uint6
     in.n_subs = so[nf];
     idx->subs = SubTable(std::move(so), {});
   }
+  *out = idx.release();
+  return EMQX_GM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// emqx_gm_index_update on a sharded index (built without subscriber lists).
+// The reference applies a route delta on every node to its own tables in a
+// constant number of key writes (apps/emqx/src/emqx_router_utils.erl:33-38,
+// 74-125, emqx_trie.erl:107-136); here every shard applies its share of the
+// delta at once (one host thread and one device each):
+//   host plan  O(delta log n): the ops folded against the global filter table,
+//              the global id shift G, each op's shard under the fixed route;
+//   per shard  PATCH   local changes that fit: patch_update on the shard (its
+//                      mirror) + its new id map in the same device step;
+//              SHIFT   no local change: the previous shard's tables shared
+//                      (blob_owner), a new id map only;
+//              REBUILD no room / delta past max(4096, n_local / 8) / a '#'
+//                      before a new filter's last word / the mirror moved on:
+//                      build_index of this shard's updated filters alone;
+//   host side  one merge pass per shard over its u32 id map (its own thread),
+//              one over the top-level fshard (a thread of its own): 4 B read
+//              and written per filter; no filter bytes of unchanged filters
+//              are walked.
+// The balance of the shards drifts with the updates until a rebuild re-plans.
+// ---------------------------------------------------------------------------
+namespace {
+thread_local std::vector<uint32_t> tl_shard_kinds;
+
+struct ShardPlan {
+  std::set<uint32_t> tomb;        // local ids deleted
+  std::set<std::string> dset;     // filters gained
+  std::vector<uint32_t> add_gid;  // ... their final global ids (byte order)
+  bool well_formed = true;
+};
+
+// The shard's id map after the update: survivors G(old id), merged with the
+// new filters' ids.  G's shift is constant between two of its list entries, so
+// the old map is cut where the shift or the kept set changes (O(delta log n)
+// searches) and every piece is copied with one constant added: a streaming
+// pass over the u32 map, no search per element.
+std::vector<uint32_t> next_gmap(const std::vector<uint32_t>& old, const ShardPlan& p, const IdShift& G) {
+  const uint64_t nl = old.size();
+  auto pos = [&](uint64_t g) { return uint64_t(std::lower_bound(old.begin(), old.end(), g) - old.begin()); };
+  std::vector<uint64_t> cut{0, nl};
+  for (uint64_t d : G.dels) cut.push_back(pos(d + 1));  // ids past d lose one more
+  for (uint64_t a : G.addpos) cut.push_back(pos(a));    // ids from a on gain one more (a local insert lands here)
+  for (uint32_t t : p.tomb) {
+    cut.push_back(t);
+    cut.push_back(uint64_t(t) + 1);
+  }
+  std::sort(cut.begin(), cut.end());
+  cut.erase(std::unique(cut.begin(), cut.end()), cut.end());
+  std::vector<uint32_t> ng(nl - p.tomb.size() + p.add_gid.size());
+  uint64_t w = 0;
+  size_t ai = 0;
+  for (size_t k = 0; k + 1 < cut.size(); ++k) {
+    const uint64_t b = cut[k], e = cut[k + 1];
+    if (p.tomb.count(uint32_t(b))) continue;  // (a deleted filter is a piece of its own)
+    const uint32_t g = old[b];
+    const int64_t c = int64_t(std::upper_bound(G.addpos.begin(), G.addpos.end(), uint64_t(g)) - G.addpos.begin()) -
+                      int64_t(std::lower_bound(G.dels.begin(), G.dels.end(), uint64_t(g)) - G.dels.begin());
+    while (ai < p.add_gid.size() && int64_t(p.add_gid[ai]) < int64_t(g) + c) ng[w++] = p.add_gid[ai++];
+    const uint32_t* src = old.data() + b;
+    uint32_t* dst = ng.data() + w;
+    const uint32_t cc = uint32_t(c);  // (mod 2^32: the sum is exact)
+    for (uint64_t t = 0; t < e - b; ++t) dst[t] = src[t] + cc;
+    w += e - b;
+  }
+  while (ai < p.add_gid.size()) ng[w++] = p.add_gid[ai++];
+  return ng;
+}
+}  // namespace
+
+const std::vector<uint32_t>& last_shard_kinds() { return tl_shard_kinds; }
+
+int update_sharded(emqx_gm_ctx* ctx, emqx_gm_index* prev, const uint8_t* fb, const uint64_t* fo, const uint8_t* ops,
+                   uint64_t n_ops, emqx_gm_index** out) {
+  tl_shard_kinds.clear();
+  if (!prev || !out) return set_err(ctx, EMQX_GM_EINVAL, "index_update: NULL argument");
+  if (n_ops && (!fb || !fo || !ops)) return set_err(ctx, EMQX_GM_EINVAL, "index_update: NULL op buffers");
+  if (!prev->subs.empty())
+    return set_err(ctx, EMQX_GM_EUNSUPPORTED, "index_update: sharded index with subscriber lists (rebuild it)");
+  const std::vector<emqx_gm_ctx*> mem = devices_of(ctx);
+  const int K = int(prev->shards.size());
+  if (K > int(mem.size()) || route_n_shards(prev->route) != uint32_t(K))
+    return set_err(ctx, EMQX_GM_EINVAL, "index_update: a sharded index of another context");
+  tl_ustats.replica_mode = EMQX_GM_REP_SHARDED;
+  tl_ustats.replicas = uint32_t(K - 1);
+  // ---- the ops folded against the global filter table (update_index's rules)
+  std::set<uint32_t> tomb;
+  std::set<std::string> dset;
+  for (uint64_t i = 0; i < n_ops; ++i) {
+    if (fo[i + 1] < fo[i]) return set_err(ctx, EMQX_GM_EINVAL, "index_update: offsets not monotone");
+    const uint8_t* f = fb + fo[i];
+    const uint64_t len = fo[i + 1] - fo[i];
+    if (len >= (1ull << 31)) return set_err(ctx, EMQX_GM_EINVAL, "index_update: filter too long");
+    bool found;
+    const uint64_t b = prev->ft.rank_of(f, len, &found);
+    if (ops[i]) {  // insert (idempotent)
+      if (found) tomb.erase(uint32_t(b));
+      else dset.emplace(reinterpret_cast<const char*>(f), len);
+    } else {  // delete (only if present)
+      if (found) tomb.insert(uint32_t(b));
+      else dset.erase(std::string(reinterpret_cast<const char*>(f), len));
+    }
+  }
+  if (tomb.empty() && dset.empty()) {
+    prev->refs.fetch_add(1);
+    *out = prev;
+    tl_ustats.kind = EMQX_GM_UPD_NONE;
+    return EMQX_GM_OK;
+  }
+  // ---- the global id shift and each new filter's final id and shard
+  const uint64_t nb = prev->info.n_filters, na = dset.size();
+  if (nb + na >= 0x7FFFFFFFull) return set_err(ctx, EMQX_GM_EINVAL, "index_update: too many filters");
+  IdShift G;
+  G.nb = nb;
+  G.dels.assign(tomb.begin(), tomb.end());
+  G.addpos.reserve(na);
+  uint64_t twild = 0, dwild = 0;
+  for (const std::string& d : dset) {
+    bool found;
+    G.addpos.push_back(prev->ft.rank_of(reinterpret_cast<const uint8_t*>(d.data()), d.size(), &found));
+    dwild += is_wild(reinterpret_cast<const uint8_t*>(d.data()), d.size());
+  }
+  std::vector<ShardPlan> P(K);
+  auto each_shard = [&](uint32_t s, auto f) -> bool {
+    if (s == EMQX_GM_ALL_SHARDS) {
+      for (int k = 0; k < K; ++k) f(k);
+      return true;
+    }
+    if (s >= uint32_t(K)) return false;
+    f(int(s));
+    return true;
+  };
+  bool ok = true, stray = false;  // stray: a deleted filter missing from its shard's id map
+  for (uint32_t g : tomb) {
+    uint64_t l;
+    const uint8_t* p = prev->ft.at(g, &l);
+    twild += is_wild(p, l);
+    ok = ok && each_shard(prev->fshard[g], [&](int k) {
+      const std::vector<uint32_t>& gm = prev->shards[k]->gmap;
+      auto it = std::lower_bound(gm.begin(), gm.end(), g);
+      if (it == gm.end() || *it != g) stray = true;
+      else P[k].tomb.insert(uint32_t(it - gm.begin()));
+    });
+  }
+  std::vector<uint32_t> add_shard(na);
+  {
+    uint64_t j = 0;
+    for (const std::string& d : dset) {
+      const uint8_t* p = reinterpret_cast<const uint8_t*>(d.data());
+      const uint32_t gid = G.map(nb + j), s = route_filter_shard(prev->route, p, d.size());
+      const bool wf = well_formed_filter(p, d.size());
+      add_shard[j++] = s;
+      ok = ok && each_shard(s, [&](int k) {
+        P[k].dset.insert(d);
+        P[k].add_gid.push_back(gid);
+        P[k].well_formed = P[k].well_formed && wf;
+      });
+    }
+  }
+  if (!ok || stray) return set_err(ctx, EMQX_GM_EINVAL, "index_update: the sharded index's shard tables disagree");
+  // ---- the top-level filter -> shard table, merged on a thread of its own
+  const uint64_t nf_new = nb - tomb.size() + na;
+  std::vector<uint32_t> nfshard;
+  std::thread fshard_thread([&] {  // (pieces between two changes copied whole)
+    nfshard.resize(nf_new);
+    const uint32_t* src = prev->fshard.data();
+    uint32_t* dst = nfshard.data();
+    uint64_t g = 0, w = 0, d = 0, a = 0;
+    const uint64_t nd = G.dels.size();
+    auto copy_to = [&](uint64_t end) {
+      if (end > g) std::memcpy(dst + w, src + g, (end - g) * 4);
+      w += end - g;
+      g = end;
+    };
+    while (d < nd || a < na) {
+      copy_to(std::min(d < nd ? G.dels[d] : nb, a < na ? G.addpos[a] : nb));
+      while (a < na && G.addpos[a] == g) dst[w++] = add_shard[a++];
+      if (d < nd && G.dels[d] == g) {
+        ++d;
+        ++g;
+      }
+    }
+    copy_to(nb);
+  });
+  struct Joiner {
+    std::thread& t;
+    ~Joiner() {
+      if (t.joinable()) t.join();
+    }
+  } fshard_join{fshard_thread};
+  // ---- every shard at once: patch, shift or rebuild
+  std::vector<emqx_gm_index*> ns(K, nullptr);
+  std::vector<uint32_t> kinds(K, EMQX_GM_UPD_SHIFT);
+  std::vector<emqx_gm_update_stats> st(K);
+  auto shard_step = [&](int k) -> int {
+    emqx_gm_ctx* c = mem[k];
+    emqx_gm_index* s = prev->shards[k];
+    const ShardPlan& p = P[k];
+    const uint64_t nl = s->info.n_filters, delta = p.tomb.size() + p.dset.size();
+    std::vector<uint32_t> ng = next_gmap(s->gmap, p, G);
+    emqx_gm_index* o = nullptr;
+    if (!delta) {
+      // no local change: the previous shard's tables shared, a new id map only
+      o = new emqx_gm_index;
+      o->device = s->device;
+      emqx_gm_index* owner = s->blob_owner ? s->blob_owner : s;
+      owner->refs.fetch_add(1);
+      o->blob_owner = owner;
+      o->dev_base = s->dev_base;
+      o->dev_bytes = s->dev_bytes;
+      o->view = s->view;
+      o->dev_flen = s->dev_flen;
+      o->flen_stale = s->flen_stale.load();
+      o->ft = s->ft;
+      o->level_nodes = s->level_nodes;
+      o->info = s->info;
+      {  // the mirror follows the newest snapshot of the shard's line
+        std::lock_guard<std::mutex> ml(s->mirror_mu);
+        o->mirror = s->mirror;
+        s->mirror = nullptr;
+      }
+      const double t0 = now_ms();
+      const hipError_t e = hipMalloc(&o->dev_gmap, (nl + 1) * 4);
+      if (e != hipSuccess) {
+        o->dev_gmap = nullptr;
+        free_index(o);
+        return set_err(c, EMQX_GM_ENOMEM, std::string("index_update: hipMalloc (id map): ") + hipGetErrorString(e));
+      }
+      const std::vector<uint32_t> none;
+      GmapJob job;
+      job.old_gmap = s->view.gmap;
+      job.nb = nl;
+      job.sh = GmapShift{&G, &none};
+      job.new_gmap = static_cast<uint32_t*>(o->dev_gmap);
+      job.n_new = nl;
+      if (const int rc = shift_gmap_device(c, job)) {
+        free_index(o);
+        return rc;
+      }
+      o->view.gmap = job.new_gmap;
+      tl_ustats.device_ms = now_ms() - t0;
+      kinds[k] = EMQX_GM_UPD_SHIFT;
+    } else {
+      bool patched = false;
+      if (delta <= std::max<uint64_t>(4096, nl / 8) && p.well_formed) {
+        std::lock_guard<std::mutex> ml(s->mirror_mu);
+        if (s->mirror) {
+          const GmapShift gs{&G, &p.add_gid};
+          const int rc = patch_update(c, s, p.tomb, p.dset, &o, nullptr, false, nullptr, &gs);
+          if (rc < 0) return rc;
+          patched = rc == 0;  // (1: a table has no room, nothing changed)
+        }
+      }
+      if (patched) {
+        kinds[k] = EMQX_GM_UPD_PATCH;
+      } else {
+        // this shard alone recompiled, with its filters' new global ids
+        std::vector<uint8_t> b;
+        std::vector<uint64_t> off{0};
+        auto dit = p.dset.begin();
+        auto tit = p.tomb.begin();
+        auto put = [&](const uint8_t* q, uint64_t l) {
+          b.insert(b.end(), q, q + l);
+          off.push_back(b.size());
+        };
+        s->ft.for_each([&](uint64_t i, const uint8_t* bp, uint64_t bl) {
+          while (dit != p.dset.end() &&
+                 cmp_filter(reinterpret_cast<const uint8_t*>(dit->data()), dit->size(), bp, bl) < 0) {
+            put(reinterpret_cast<const uint8_t*>(dit->data()), dit->size());
+            ++dit;
+          }
+          if (tit != p.tomb.end() && *tit == i) {
+            ++tit;
+            return;
+          }
+          put(bp, bl);
+        });
+        for (; dit != p.dset.end(); ++dit) put(reinterpret_cast<const uint8_t*>(dit->data()), dit->size());
+        b.resize(b.size() + 64, 0);
+        const uint64_t n = off.size() - 1;
+        if (n != ng.size()) return set_err(c, EMQX_GM_EINVAL, "index_update: shard id map out of step");
+        std::vector<uint32_t> perm(n + 1);
+        const double t0 = now_ms();
+        if (const int rc = build_index(c, b.data(), off.data(), n, nullptr, nullptr, perm.data(), &o, nullptr,
+                                       n ? ng.data() : nullptr, true))
+          return rc;
+        tl_ustats.device_ms = now_ms() - t0;
+        kinds[k] = EMQX_GM_UPD_REBUILD;
+      }
+    }
+    if (o->dev_gmap) {
+      o->gmap = std::move(ng);
+      o->info.device_bytes = o->dev_bytes + (o->gmap.size() + 1) * 4;
+    }
+    ns[k] = o;
+    return 0;
+  };
+  const int rc = run_all(K, [&](int k) -> int {
+    MemberLock lk(mem[k]);
+    const emqx_gm_update_stats saved = tl_ustats;  // (shard 0 runs on the calling thread)
+    tl_ustats = emqx_gm_update_stats{};
+    const int r = shard_step(k);
+    st[k] = tl_ustats;
+    tl_ustats = saved;
+    return r;
+  });
+  fshard_thread.join();
+  hipSetDevice(ctx->device);
+  if (rc) {  // (a shard patched before another failed took its line's mirror with it: prev's next update rebuilds that shard)
+    for (emqx_gm_index* o : ns) free_index(o);
+    return rc;
+  }
+  // ---- the host side of the new snapshot
+  std::unique_ptr<emqx_gm_index> idx(new emqx_gm_index);
+  idx->device = ctx->device;
+  retain_route(prev->route);
+  idx->route = prev->route;
+  idx->shards = ns;
+  idx->fshard = std::move(nfshard);
+  idx->ft = prev->ft.apply(G.dels, dset);
+  emqx_gm_index_info_t& in = idx->info;
+  in.n_filters = nf_new;
+  in.n_wildcard = prev->info.n_wildcard - twild + dwild;
+  in.trie_empty = in.n_wildcard == 0;
+  bool rebuilt = false;
+  for (int k = 0; k < K; ++k) {
+    const emqx_gm_index* s = ns[k];
+    in.n_nodes += s->info.n_nodes;
+    in.n_edges += s->info.n_edges;
+    in.n_words = std::max(in.n_words, s->info.n_words);
+    in.device_bytes += s->info.device_bytes;
+    in.max_depth = std::max(in.max_depth, s->info.max_depth);
+    rebuilt = rebuilt || kinds[k] == EMQX_GM_UPD_REBUILD;
+    tl_ustats.device_ms = std::max(tl_ustats.device_ms, st[k].device_ms);
+    tl_ustats.blobs_reused += st[k].blobs_reused;
+    tl_ustats.blobs_fresh += st[k].blobs_fresh;
+    tl_ustats.mirror_loaded = tl_ustats.mirror_loaded || st[k].mirror_loaded;
+    tl_ustats.mirror_bytes += st[k].mirror_bytes;
+    tl_ustats.mirror_ms = std::max(tl_ustats.mirror_ms, st[k].mirror_ms);
+  }
+  tl_ustats.kind = rebuilt ? EMQX_GM_UPD_REBUILD : EMQX_GM_UPD_PATCH;
+  tl_shard_kinds = kinds;
   *out = idx.release();
   return EMQX_GM_OK;
 }

@@ -527,6 +527,18 @@ class Context:
         d["mirror_loaded"] = bool(d["mirror_loaded"])
         return d
 
+    last_update_stats = update_stats
+
+    def last_shard_update(self) -> List[str]:
+        """What each shard of this thread's last update of a sharded index did
+        (emqx_gm_last_shard_update): "patch" (patched in place), "shift" (no local
+        change: tables shared, a new id map only) or "rebuild" (recompiled alone)."""
+        n = C.c_uint32(0)
+        check(lib().emqx_gm_last_shard_update(self.h, None, C.byref(n)), self.h, "last_shard_update")
+        kinds = np.zeros(max(int(n.value), 1), np.uint32)
+        check(lib().emqx_gm_last_shard_update(self.h, _ptr(kinds), C.byref(n)), self.h, "last_shard_update")
+        return [_lib.UPD_KINDS.get(int(k), int(k)) for k in kinds[:int(n.value)]]
+
     def last_kernel_ms(self) -> float:
         """stats()["match_kernel_ms"] without building the dict (a serving loop's per-call read)."""
         s = self._stats_buf
@@ -618,6 +630,16 @@ class Route:
         check(lib().emqx_gm_route_topics_host(self.h, _ptr(tb), _ptr(to), n, _ptr(out)), None, "route_topics_host")
         return out[:n]
 
+    def filter_shards(self, fb: np.ndarray, fo: np.ndarray) -> np.ndarray:
+        """Each filter's shard under this route as it stands (ALL_SHARDS: every
+        shard) -- where a sharded update puts a new filter
+        (emqx_gm_route_filter_shards_host)."""
+        n = len(fo) - 1
+        out = np.zeros(max(n, 1), np.uint32)
+        check(lib().emqx_gm_route_filter_shards_host(self.h, _ptr(fb), _ptr(fo), n, _ptr(out)), None,
+              "route_filter_shards_host")
+        return out[:n]
+
     def release(self):
         if self.h:
             lib().emqx_gm_route_release(self.h)
@@ -628,6 +650,9 @@ class Route:
             self.release()
         except Exception:
             pass
+
+
+RoutePlan = Route
 
 
 def prefix_plan(fb: np.ndarray, fo: np.ndarray, n_shards: int) -> Tuple[np.ndarray, "Route"]:

@@ -76,10 +76,12 @@ int emqx_gm_fanout_part(emqx_gm_ctx *ctx, const emqx_gm_index *idx, const emqx_g
 #define EMQX_GM_UPD_SUBS_ONLY 4 /* update_subs without a route change: tables shared   */
 #define EMQX_GM_UPD_BUILD 5
 #define EMQX_GM_UPD_IMPORT 6
+#define EMQX_GM_UPD_SHIFT 7     /* a shard of a sharded update: ids only, tables shared */
 #define EMQX_GM_REP_NONE 0      /* no replicas (single device, or left on the first)   */
 #define EMQX_GM_REP_PATCHED 1   /* every member applied the same delta to its replica  */
 #define EMQX_GM_REP_COPIED 2    /* device tables copied device to device (tree order)  */
 #define EMQX_GM_REP_SHARED 3    /* members share their replica's tables + own new CSR  */
+#define EMQX_GM_REP_SHARDED 4  /* a sharded index: every shard applied its share (replicas = shards - 1) */
 typedef struct {
   uint32_t kind;          /* EMQX_GM_UPD_*                                        */
   uint32_t replica_mode;  /* EMQX_GM_REP_*                                        */
@@ -94,6 +96,26 @@ typedef struct {
   uint32_t blobs_fresh;   /* ... in a fresh allocation (every device counted)     */
 } emqx_gm_update_stats;
 int emqx_gm_last_update_stats(const emqx_gm_ctx *ctx, emqx_gm_update_stats *stats);
+/* What each shard of the calling thread's last emqx_gm_index_update on a
+ * sharded index did: EMQX_GM_UPD_PATCH (patched in place), EMQX_GM_UPD_SHIFT
+ * (no local change: the previous tables shared, a new id map only) or
+ * EMQX_GM_UPD_REBUILD (this shard recompiled alone).  The stats of such an
+ * update: kind PATCH when no shard was recompiled, REBUILD when any was, NONE
+ * for no change; replica_mode EMQX_GM_REP_SHARDED, replicas = shards - 1.
+ * In: *n = the entries `kinds` holds (kinds may be NULL); out: *n = the
+ * shards (0: the thread has made no sharded update, or its last one changed
+ * nothing). */
+int emqx_gm_last_shard_update(const emqx_gm_ctx *ctx, uint32_t *kinds, uint32_t *n);
+/* shard_out[i] = the shard a filter goes to under a FIXED route (what a
+ * sharded update does with a new filter; no re-plan, no newly split word):
+ * EMQX_GM_ALL_SHARDS for a first word '+' / '#', and under a split (hot)
+ * first word for the word alone or a '+' / '#' second word; else the shard
+ * emqx_gm_route_topics_host gives the filter's own bytes read as a topic.
+ * For every filter the plan was made from this is the plan's shard_out; for
+ * any other it is the shard every topic able to match the filter is routed
+ * to.  Host buffers. */
+int emqx_gm_route_filter_shards_host(const emqx_gm_route *route, const uint8_t *filter_bytes,
+                                     const uint64_t *filter_off, uint64_t n_filters, uint32_t *shard_out);
 
 /* Test support: FNV-1a digests of replica k's device tables (k = 0: the
  * snapshot itself, k >= 1: its replica on the context's k-th member) and of

@@ -232,8 +232,19 @@ int emqx_gm_index_build(emqx_gm_ctx *ctx, const uint8_t *filter_bytes, const uin
  * snapshot shares prev's tables (tombstones + a delta index; emqx_gm_fanout
  * refuses it).  Past 1/8 of the set, or when the tables run out of headroom,
  * the set is rebuilt.  Ids in rows of the new snapshot are ranks in the
- * updated set, as a full rebuild would give.  Not available for shard indexes
- * or indexes with subscriber lists (EMQX_GM_EUNSUPPORTED: rebuild those). */
+ * updated set, as a full rebuild would give.
+ * A prefix-sharded index (emqx_gm_index_build_sharded) built WITHOUT
+ * subscriber lists is updated the same way, shard by shard and all devices at
+ * once: the route is fixed, so a new filter goes to the shard its matching
+ * topics are routed to; a shard with changes is patched in place (or, without
+ * room or mirror, recompiled alone), a shard without any shares its previous
+ * tables, and every shard gets a new local-to-global id map from one device
+ * pass.  Rows of the result are bit-equal to a fresh sharded or unsharded
+ * build of the updated set; a batch with no net change returns `prev`
+ * retained.  Not available for stand-alone shard indexes
+ * (emqx_gm_index_build_shard) or indexes -- sharded ones included -- with
+ * subscriber lists (EMQX_GM_EUNSUPPORTED: rebuild those, or use
+ * emqx_gm_index_update_subs on a plain one). */
 int emqx_gm_index_update(emqx_gm_ctx *ctx, emqx_gm_index *prev, const uint8_t *filter_bytes,
                          const uint64_t *filter_off, const uint8_t *ops, uint64_t n_ops, emqx_gm_index **out);
 /* Subscriber maintenance on an index built with subscriber lists
@@ -396,9 +407,13 @@ int emqx_gm_prefix_plan(const uint8_t *filter_bytes, const uint64_t *filter_off,
  * matches every device's topics there at the same time and returns the rows in
  * batch order (global ids, bit-exact with an unsharded index); emqx_gm_fanout
  * on host rows fans each row out on its shard; emqx_gm_index_info / _filter /
- * _subscriber_count answer for the whole set.  Device-buffer calls, updates and
- * images of a sharded index: EMQX_GM_EUNSUPPORTED (a global id shifts on every
- * shard when one filter is added: rebuild it).  Arguments as emqx_gm_index_build. */
+ * _subscriber_count answer for the whole set.  emqx_gm_index_update takes a
+ * sharded index built without subscriber lists (see there); on such an index
+ * emqx_gm_fanout gives no deliveries.  Still EMQX_GM_EUNSUPPORTED on a sharded
+ * index: emqx_gm_index_update when it was built with subscriber lists,
+ * emqx_gm_index_update_subs (out of scope: subscriber changes of a sharded set
+ * need a rebuild), images and device-buffer calls.  Arguments as
+ * emqx_gm_index_build. */
 int emqx_gm_index_build_sharded(emqx_gm_ctx *ctx, const uint8_t *filter_bytes, const uint64_t *filter_off,
                                 uint64_t n_filters, const uint64_t *sub_off, const uint32_t *sub_ids,
                                 uint32_t *perm_out, emqx_gm_index **out);

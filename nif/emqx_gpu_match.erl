@@ -39,7 +39,10 @@ load_index(_Filters, _SubIds) -> erlang:nif_error(nif_not_loaded).
 %% A route table too large for one GPU: the filters partitioned by first word
 %% over the node's GPUs (the NIF context's device list), each topic matched on
 %% its one GPU (emqx_gm_index_build_sharded).  Used like any index by the match
-%% and fan-out calls; updates and exports of it return {error, _}: rebuild it.
+%% and fan-out calls.  update_index/2 works on a table loaded without subscriber
+%% ids (load_index_sharded/1); with subscriber ids (load_index_sharded/2) it is
+%% rebuild-only, and update_subs/2 and export_index/1 return {error, _} for any
+%% sharded table.
 -spec load_index_sharded([binary()]) -> {ok, reference()} | {error, term()}.
 load_index_sharded(_Filters) -> erlang:nif_error(nif_not_loaded).
 
@@ -48,6 +51,7 @@ load_index_sharded(_Filters, _SubIds) -> erlang:nif_error(nif_not_loaded).
 
 %% Route changes (do_add_route/do_delete_route) as one batch -> a new snapshot;
 %% the old one stays valid for readers holding it (emqx_gm_index_update).
+%% Also on a table from load_index_sharded/1: each GPU applies its share.
 %% Any op other than insert | delete is badarg.
 -spec update_index(reference(), [{binary(), insert | delete}]) -> {ok, reference()} | {error, term()}.
 update_index(_Index, _Ops) -> erlang:nif_error(nif_not_loaded).

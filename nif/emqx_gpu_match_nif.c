@@ -239,8 +239,12 @@ static ERL_NIF_TERM load_index(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv
  * one GPU: the filters partitioned by first word over the context's devices
  * (emqx_gm_index_build_sharded), each topic matched on its one device.
  * match_batch/2, match_routes_batch/2 and fanout_batch/2 take the result like
- * any index; update_index/2, update_subs/2 and export_index/1 return
- * {error, Reason} for it (EMQX_GM_EUNSUPPORTED: rebuild it). */
+ * any index.  update_index/2 works on a table from load_index_sharded/1 (no
+ * subscriber ids): every device patches its share of the batch at once.  A
+ * table from load_index_sharded/2 (with subscriber ids) is rebuild-only:
+ * update_index/2 and update_subs/2 return {error, Reason} for it, as
+ * update_subs/2 and export_index/1 do for any sharded table
+ * (EMQX_GM_EUNSUPPORTED). */
 static ERL_NIF_TERM load_index_sharded(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
   return do_load(env, argc, argv, 1);
 }
