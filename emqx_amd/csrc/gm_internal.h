@@ -211,6 +211,22 @@ inline const char* knob(const char* name) {
   return getenv(name);
 }
 
+// Whether a match call on view v takes the flat instantiations of the walk
+// kernels: a table the buffer form could not address with 32-bit byte offsets
+// under a 2 GiB descriptor (a hot table: IX_HOT_FLAT, set at build; the word
+// dictionary, an MPH table's bucket words, an exact-edge filter), or the
+// GM_HOT_FLAT test knob.
+inline bool view_flat(const IndexView& v) {
+  constexpr uint64_t LIM = 1ull << 31;
+  if (v.flags & IX_HOT_FLAT) return true;
+  if ((v.dict_mask + 1) * sizeof(DictSlot) >= LIM) return true;
+  for (int t = 0; t < HOT_TABLES; ++t)
+    if (v.hot_cap[t] * sizeof(HotSlot) >= LIM || uint64_t(v.mph_nb[t]) * 8 >= LIM ||
+        (uint64_t(v.efilt_mask[t]) + 1) * 4 >= LIM)
+      return true;
+  return false;
+}
+
 // What the calling thread's last index call did (emqx_gm_last_update_stats):
 // the entry points reset it, the update paths fill it in.
 extern thread_local emqx_gm_update_stats tl_ustats;

@@ -69,6 +69,20 @@ __device__ __forceinline__ void st_s(T* p, T v) {
   else *p = v;
 }
 
+// Diagnostic build only (-DGM_ISSUE_PAD=N, the Makefile's diag target): N
+// v_nop and N s_nop 0 per walk round and per tokenized word of the fused
+// kernel.  The kernel time against N is the cost of an issued instruction
+// (profiles/issue/step0.txt); the product defines nothing.
+#ifdef GM_ISSUE_PAD
+#define GM_STR_(x) #x
+#define GM_STR(x) GM_STR_(x)
+#define GM_PAD() asm volatile(".rept " GM_STR(GM_ISSUE_PAD) "\n v_nop\n s_nop 0\n .endr")
+#else
+#define GM_PAD() \
+  do {           \
+  } while (0)
+#endif
+
 // Byte reader over a lane's topic with an 8-byte cache (aligned 8-B loads;
 // topic buffers are padded, emqx_gpu_match.h).
 struct ByteReader {
@@ -226,6 +240,76 @@ struct HotRec {
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t hot_rsrc(const HotSlot* tab) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<HotSlot*>(tab), (short)0, 0x7FFFFFFF, 0x00020000);
 }
+// One table (or one level's part of it) as k_match_fused and k_walk_coop read
+// it.  FLAT false: through a buffer resource of the table's real byte size,
+// built from wave-uniform values only (kernel arguments, a readfirstlane'd
+// level), with 32-bit per-lane byte offsets -- no 64-bit address arithmetic per
+// lane, and the hardware range check drops the request of a lane that passes
+// OOB (it reads zeros), so a load whose lanes do not all want it needs no
+// exec-mask branch.  FLAT true (a table of 2 GiB or more, IX_HOT_FLAT): flat
+// loads under the predicate.  The caller selects by the predicate, never by
+// the loaded value.
+constexpr uint32_t OOB = 0x80000000u;  // a byte offset no buffer table reaches
+// Which buffer loads every lane issues (the range check drops the lanes that
+// pass OOB) instead of sitting under an exec-mask branch: a bit mask per site
+// group (-DGM_PRED_LOADS=m for an A/B build).  At C2 against none (8.03 ms):
+// the dictionary -0.03 ms, the tails and level 0 -0.03 ms, the MPH / filter
+// words +0.11 ms, the hot-slot probes +0.28 ms -- a probe
+// most lanes skip costs its address cycles whether or not the range check
+// drops it, a branch around it does not.
+#ifndef GM_PRED_LOADS
+#define GM_PRED_LOADS 9
+#endif
+constexpr bool PR_DICT = (GM_PRED_LOADS & 1) != 0;  // the tokenizer's first dictionary slots
+constexpr bool PR_GATE = (GM_PRED_LOADS & 2) != 0;  // MPH bucket words, exact-edge filter words
+constexpr bool PR_HOT = (GM_PRED_LOADS & 4) != 0;   // the hot-slot probes
+constexpr bool PR_TAIL = (GM_PRED_LOADS & 8) != 0;  // chain tails, the level-0 probe and its end filter
+template <bool FLAT>
+struct TabRef {
+  const uint8_t* p;
+  __amdgpu_buffer_rsrc_t rs;
+  __device__ __forceinline__ TabRef(const void* base, uint32_t bytes)
+      : p(static_cast<const uint8_t*>(base)),
+        rs(__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, int(FLAT ? 0u : bytes), 0x00020000)) {}
+  // element i of ESZ bytes, byte `sub` within it (32-bit byte offsets in the
+  // buffer form, 64-bit addresses in the flat form)
+  template <uint32_t ESZ>
+  __device__ __forceinline__ const uint8_t* at(uint32_t i, uint32_t sub) const {
+    return p + uint64_t(i) * ESZ + sub;
+  }
+  // pol (wave-uniform): hot_load's cache policies; only the A/B instantiations pass one
+  template <uint32_t ESZ>
+  __device__ __forceinline__ uint4 ld128(uint32_t i, uint32_t sub, bool pred, bool pr, uint32_t pol = 0) const {
+    if constexpr (FLAT) {
+      return pred ? *reinterpret_cast<const uint4*>(at<ESZ>(i, sub)) : make_uint4(0u, 0u, 0u, 0u);
+    } else {
+      if (!pr && !pred) return make_uint4(0u, 0u, 0u, 0u);
+      const uint32_t o = pred ? i * ESZ + sub : OOB;
+      const auto v = pol == 0 ? __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, 0)
+                     : pol == 1 ? __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, 16)
+                     : pol == 2 ? __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, 17)
+                     : pol == 3 ? __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, 2)
+                                : __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, 18);
+      return make_uint4(v[0], v[1], v[2], v[3]);
+    }
+  }
+  template <uint32_t ESZ>
+  __device__ __forceinline__ uint2 ld64(uint32_t i, bool pred, bool pr) const {
+    if constexpr (FLAT) {
+      return pred ? *reinterpret_cast<const uint2*>(at<ESZ>(i, 0)) : make_uint2(0u, 0u);
+    } else {
+      if (!pr && !pred) return make_uint2(0u, 0u);
+      const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, pred ? i * ESZ : OOB, 0, 0);
+      return make_uint2(v[0], v[1]);
+    }
+  }
+  template <uint32_t ESZ>
+  __device__ __forceinline__ uint32_t ld32(uint32_t i, uint32_t sub, bool pred, bool pr) const {
+    if constexpr (FLAT) return pred ? *reinterpret_cast<const uint32_t*>(at<ESZ>(i, sub)) : 0u;
+    if (!pr && !pred) return 0u;
+    return __builtin_amdgcn_raw_buffer_load_b32(rs, pred ? i * ESZ + sub : OOB, 0, 0);
+  }
+};
 // pol (wave-uniform; 0 = default): the cache policy of a probe of a table
 // selected by IndexView::l1_bypass (A/B knobs GM_L1_BYPASS, GM_HOT_POLICY):
 // 1 sc1 (no L1 fill), 2 sc0 sc1 (system scope), 3 nt, 4 sc1 nt
@@ -280,13 +364,6 @@ __device__ __forceinline__ uint32_t hot_home(const IndexView& ix, int ht, uint64
     return mph_slot(key, uint32_t(w) & 0xFFFFu, mc);
   }
   return uint32_t(hot_slot(key, cap));
-}
-// An MPH table's bucket word for `key` (one L2 read): whether the table may
-// hold the key (its Bloom bits) and, if so, the key's perfect slot.
-__device__ __forceinline__ bool mph_gate(const IndexView& ix, int ht, uint64_t key, uint32_t mc, uint32_t& s) {
-  const uint64_t w = ix.mph_word[ix.mph_off[ht] + mph_bucket(key, ix.mph_nb[ht])];
-  s = mph_slot(key, uint32_t(w) & 0xFFFFu, mc);
-  return mph_may_hold(w, key);
 }
 // hot_resolve for either kind of table: an MPH table's key is at its perfect
 // slot, or (once an in-place update put keys there) in the overflow region.
@@ -383,15 +460,6 @@ __device__ __forceinline__ HotRec plus_inline_load(const HotSlot* ptab, uint32_t
   r.a = make_uint4(0u, 0u, q.y, q.z);
   r.ef = q.w;
   return r;
-}
-// The second 16 bytes of slot s: {end_filter, p_sig, p_hf, p_end} (a chain
-// node's tail: {end_filter, s2, HF_NONE, F}).
-__device__ __forceinline__ uint4 hot_tail_load(const HotSlot* tab, uint32_t s, bool flat) {
-  if (!flat) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(hot_rsrc(tab), s * 32u + 16u, 0, 0);
-    return make_uint4(v[0], v[1], v[2], v[3]);
-  }
-  return *reinterpret_cast<const uint4*>(reinterpret_cast<const uint32_t*>(tab + s) + 4);
 }
 // Whether the '+' child of frontier entry `id` (a node at depth lvl) is inline.
 __device__ __forceinline__ bool plus_is_inline(uint32_t lvl, uint32_t id) { return plus_inline(lvl, !(id & HOT_INLINE)); }
@@ -759,11 +827,15 @@ struct WidsToRegs {
   }
 };
 
-template <int G, class SINK>
+// DBUF (k_match_fused's buffer form): the words' first dictionary slots are
+// raw buffer loads (32-bit offsets from ix.dict) that every lane issues; a
+// lane without a word at that level passes an out-of-range offset.
+template <int G, bool DBUF = false, class SINK>
 __device__ __forceinline__ uint32_t tokenize_grouped(const uint64_t* lds, uint32_t pos, uint32_t end,
                                                      const IndexView& ix, const uint8_t* tb_lo, SINK&& sink) {
   uint32_t lev = 0, fl = 0;
   bool more = true, wild = false;
+  const TabRef<!DBUF> DT(ix.dict, uint32_t(ix.dict_mask + 1) * uint32_t(sizeof(DictSlot)));
   while (more && lev < uint32_t(TOK_LMAX)) {
     uint64_t hd[G];
     uint32_t hh[G], sl[G];
@@ -772,7 +844,9 @@ __device__ __forceinline__ uint32_t tokenize_grouped(const uint64_t* lds, uint32
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       have[g] = more && lev + g < uint32_t(TOK_LMAX);
+      if constexpr (DBUF) hh[g] = 0u;
       if (have[g]) {
+        GM_PAD();
         const WordTok w = next_word_s(lds, pos, end);
         if (g == 0 && lev == 0 && w.len > 0 && w.b0 == '$') fl |= TOK_DOLLAR;  // emqx_trie.erl:271-278
         if (w.len == 1 && (w.b0 == '+' || w.b0 == '#')) {  // emqx_topic:wildcard/1
@@ -782,10 +856,16 @@ __device__ __forceinline__ uint32_t tokenize_grouped(const uint64_t* lds, uint32
           hd[g] = w.head;
           hh[g] = w.h;
           sl[g] = uint32_t(w.start) | (w.len << 16);
-          d[g] = dict_first(ix, w);
+          if constexpr (!DBUF) d[g] = dict_first(ix, w);
           more = pos < end;
           pos += more ? 1u : 0u;
         }
+      }
+      if constexpr (DBUF) {
+        const uint4 q = DT.template ld128<sizeof(DictSlot)>(uint32_t(dict_slot(hh[g], ix.dict_mask)), 0u, have[g], PR_DICT);
+        d[g].head = (uint64_t(q.y) << 32) | q.x;
+        d[g].len = q.z;
+        d[g].word = q.w;
       }
     }
 #pragma unroll
@@ -1100,8 +1180,9 @@ __device__ unsigned long long g_pstats[8][8];
 // written once at the wave's end (no atomics, no read-modify-write in the
 // walk): [0] staging, [1] tokenizer, [2+l] walk level l (l < 8) in s_memtime
 // ticks, [10] epilogue, [11] rounds of levels 0-3 (8 bits each), [12] rounds of
-// levels 4-7, [13] rounds with a chain tail load, [14..15] the wave's start
-// tick.  run_match reduces them after each call.
+// levels 4-7, [13] rounds with a chain tail load, [14] the walk in s_memtime
+// ticks and [15] in s_memrealtime ticks (100 MHz): their ratio is the
+// in-kernel clock.  run_match reduces them after each call.
 __device__ uint32_t* g_phase_rec;
 struct PhaseRec {
   uint32_t v[32];  // [16 + l] ticks of level l's rounds up to the probes' data, [24 + l] the rest of them
@@ -1168,20 +1249,106 @@ struct D0Probe {
   uint4 a;     // the home slot's head {key lo, key hi, sig, hf}
   uint32_t s;  // its slot index, or NONE
 };
+
+// ---- the coop walk's table reads through TabRef ----------------------------
+// (hot_load, hot_resolve_x, ... above with every lane's request under a
+// predicate instead of a branch; a lane with pred false gets zeros)
+constexpr uint32_t HS = sizeof(HotSlot);
+template <bool FLAT>
+__device__ __forceinline__ HotRec hot_load_t(const TabRef<FLAT>& T, uint32_t s, bool with_end, bool pred,
+                                             uint32_t pol = 0) {
+  HotRec r;
+  r.a = T.template ld128<HS>(s, 0u, pred, PR_HOT, pol);
+  const uint32_t ef = T.template ld32<HS>(s, 16u, pred && with_end, PR_HOT);
+  r.ef = with_end ? ef : NONE;
+  return r;
+}
+template <bool FLAT>
+__device__ __forceinline__ HotRec plus_inline_load_t(const TabRef<FLAT>& PT, uint32_t id, bool pred) {
+  const uint4 q = PT.template ld128<HS>(id & SLOT_MASK, 16u, pred, PR_HOT);
+  HotRec r;
+  r.a = make_uint4(0u, 0u, q.y, q.z);
+  r.ef = q.w;
+  return r;
+}
+// the levels' tables of one walk level (wave-uniform): the children's hot
+// table, its MPH bucket words and its exact-edge filter
+template <bool FLAT>
+struct LevelTabs {
+  TabRef<FLAT> T, MW, FT;
+  uint32_t cap, mc, nb, fmask;
+  bool rh, ovf;
+  __device__ __forceinline__ LevelTabs(const IndexView& ix, int ht)
+      : T(ix.hot + ix.hot_off[ht], uint32_t(ix.hot_cap[ht]) * HS),
+        MW(ix.mph_word + ix.mph_off[ht], ix.mph_nb[ht] * 8u),
+        FT(ix.efilt + ix.efilt_off[ht], ix.efilt_mask[ht] ? (ix.efilt_mask[ht] + 1u) * 4u : 0u),
+        cap(uint32_t(ix.hot_cap[ht])),
+        mc(ix.mph_cap[ht]),
+        nb(ix.mph_nb[ht]),
+        fmask(ix.efilt_mask[ht]),
+        rh(((ix.rh_mask >> ht) & 1u) != 0),
+        ovf(((ix.mph_ovf >> ht) & 1u) != 0) {}
+  // an MPH table's bucket word for `key`: its perfect slot, and whether the table may hold it
+  __device__ __forceinline__ bool gate(uint64_t key, bool pred, uint32_t& s) const {
+    const uint2 w2 = MW.template ld64<8u>(mph_bucket(key, nb), pred, PR_GATE);
+    s = mph_slot(key, w2.x & 0xFFFFu, mc);
+    return pred && mph_may_hold((uint64_t(w2.y) << 32) | w2.x, key);
+  }
+  // the exact-edge filter's verdict on `key` (fmask != 0)
+  __device__ __forceinline__ bool filter(uint64_t key, bool pred) const {
+    const uint32_t fh = edge_filter_hash(key);
+    const uint32_t fb = edge_filter_bits(fh);
+    return pred && (FT.template ld32<4u>(edge_filter_word(fh, fmask), 0u, pred, PR_GATE) & fb) == fb;
+  }
+  // hot_resolve_x: the slot of `key` from its loaded home slot (s, r), or NONE
+  __device__ __forceinline__ uint32_t resolve(uint64_t key, uint32_t s, HotRec& r, bool with_end) const {
+    if (mc) {
+      if (hot_is(r, key)) return s;
+      if (!ovf) return NONE;
+      for (s = mph_ovf_home(key, mc, cap);; s = s + 1 == cap ? mc : s + 1) {
+        r = hot_load_t(T, s, with_end, true);
+        if (hot_is(r, key)) return s;
+        if (hot_empty(r)) return NONE;
+      }
+    }
+    uint32_t dist = 0;
+    while (!hot_is(r, key)) {
+      if (hot_empty(r)) return NONE;
+      if (rh) {
+        const uint32_t h = uint32_t(hot_slot((uint64_t(r.a.y) << 32) | r.a.x, cap));
+        if ((s >= h ? s - h : s + cap - h) < dist) return NONE;
+      }
+      s = s + 1 == cap ? 0 : s + 1;
+      ++dist;
+      r = hot_load_t(T, s, with_end, true);
+    }
+    return s;
+  }
+};
+
+template <bool FLAT>
 __device__ __forceinline__ D0Probe d0_issue(const IndexView& ix, uint32_t w0, uint32_t h, bool valid) {
   D0Probe p{make_uint4(0u, 0u, 0u, 0u), NONE};
   const bool walk = valid && !(h & (TOK_WILD | TOK_DEEP));
-  if (!walk || w0 == NONE || !(ix.root_sig & sig_bit(w0))) return p;
+  bool go = walk && w0 != NONE && (ix.root_sig & sig_bit(w0));
   const int ht = hot_table(1);
   const uint64_t key = hot_key(0u, w0, 0u);
+  const uint32_t cap = uint32_t(ix.hot_cap[ht]);
   uint32_t s;
   if (const uint32_t mc = ix.mph_cap[ht]) {
-    if (!mph_gate(ix, ht, key, mc, s)) return p;
+    const TabRef<FLAT> MW(ix.mph_word + ix.mph_off[ht], ix.mph_nb[ht] * 8u);
+    const uint2 w2 = MW.template ld64<8u>(mph_bucket(key, ix.mph_nb[ht]), go, PR_TAIL);
+    s = mph_slot(key, w2.x & 0xFFFFu, mc);
+    go = go && mph_may_hold((uint64_t(w2.y) << 32) | w2.x, key);
   } else {
-    s = uint32_t(hot_slot(key, ix.hot_cap[ht]));
+    s = uint32_t(hot_slot(key, cap));
   }
-  p.a = hot_load(ix.hot + ix.hot_off[ht], s, false, (ix.flags & IX_HOT_FLAT) != 0).a;
-  p.s = s;
+  const TabRef<FLAT> T(ix.hot + ix.hot_off[ht], cap * HS);
+  const uint4 a = T.template ld128<HS>(s, 0u, go, PR_TAIL);
+  if (go) {
+    p.a = a;
+    p.s = s;
+  }
   return p;
 }
 
@@ -1191,7 +1358,12 @@ __device__ __forceinline__ D0Probe d0_issue(const IndexView& ix, uint32_t w0, ui
 // round from registers does not use) and takes the root's '+' child from
 // ix.d0_root (one uniform load); the rest of the round -- visits, chains,
 // pushes, probe counts -- is the general round's.
-template <bool EXACT, bool NT, class WORDS, bool CMP = false, bool D0 = false>
+// AB false (the default instantiation of k_match_fused): none of the A/B forms
+// -- the sc1 staging store (IX_STAGE_SC1), the hot-probe cache policies
+// (l1_bypass / hot_policy), level 0 without IX_D0 -- is compiled in;
+// launch_match picks AB true whenever the call's view or knobs ask for one.
+// FLAT: the tables are read with flat loads (TabRef), chosen per index at launch.
+template <bool EXACT, bool NT, class WORDS, bool CMP = false, bool D0 = false, bool AB = true, bool FLAT = false>
 __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& words, bool valid, uint64_t t,
                                                int lane, const uint8_t* __restrict__ tb,
                                                const uint64_t* __restrict__ toff, const IndexView& ix,
@@ -1214,7 +1386,8 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
   uint4* const D1L = reinterpret_cast<uint4*>(L.e[0]);
   uint32_t* const D1S = reinterpret_cast<uint32_t*>(D1L + 64);
   static_assert(sizeof(L.e[0]) >= 64 * (sizeof(uint4) + 4), "the level-0 list holds 64 probes");
-  if (D0 && (ix.flags & IX_D0)) {
+  const bool d0 = D0 && (!AB || (ix.flags & IX_D0));  // (wave-uniform)
+  if (d0) {
     D1L[lane] = d1.a;
     D1S[lane] = d1.s;
   }
@@ -1222,6 +1395,29 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
   uint32_t* const MCNT = L.mc;
   uint2* const LW = L.lw;
   uint32_t* const stile = stage + tile * (64ull * MC);
+  // CMP: the tile's list, its row bytes and its length through buffer
+  // resources whose bases are the wave's own (readfirstlane of the two address
+  // halves: the tile offset is out of the 32-bit lane offsets, so a batch's
+  // staging may pass 4 GiB) -- one 32-bit offset per store
+  auto wave_rsrc = [](const void* q, uint32_t bytes) {
+    const uint64_t a = reinterpret_cast<uint64_t>(q);
+    // (the builtin returns int: both halves back to unsigned before they are joined)
+    const uint64_t u = (uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(a >> 32)))) << 32) |
+                       uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(a))));
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(u), (short)0, int(bytes), 0x00020000);
+  };
+  constexpr bool SBUF = CMP && !FLAT;
+  const __amdgpu_buffer_rsrc_t srs = wave_rsrc(SBUF ? stile : nullptr, SBUF ? TCAP * 4u : 0u);
+  // one entry of the list (k < TCAP); sc1: IX_STAGE_SC1 (A/B)
+  auto stage_put = [&](uint32_t k, uint32_t v, bool sc1) {
+    if constexpr (SBUF) {
+      if (AB && sc1) __builtin_amdgcn_raw_buffer_store_b32(v, srs, int(k * 4u), 0, 16);
+      else __builtin_amdgcn_raw_buffer_store_b32(v, srs, int(k * 4u), 0, NT ? 2 : 0);
+    } else {
+      stage_st<NT>(stile, k, v, AB && sc1);
+    }
+  };
+  const bool sc1st = AB && (ix.flags & IX_STAGE_SC1) != 0;
   const uint32_t nlev = h & 0xFFu;
   const bool dollar = (h & TOK_DOLLAR) != 0, wild = valid && (h & TOK_WILD), deep = valid && (h & TOK_DEEP);
   const bool walk = valid && !wild && !deep;
@@ -1235,7 +1431,7 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
   if (f0 != NONE) m0 = 1;
   if constexpr (CMP) {  // (rank 0 of the lane's row)
     const unsigned long long b0 = __ballot(f0 != NONE);
-    if (f0 != NONE) stage_st<NT>(stile, lane_prefix(b0), f0 | (uint32_t(lane) << CMP_SHIFT), ix.flags & IX_STAGE_SC1);
+    if (f0 != NONE) stage_put(lane_prefix(b0), f0 | (uint32_t(lane) << CMP_SHIFT), sc1st);
     wbase = uint32_t(__popcll(b0));
   } else {
     if (f0 != NONE) stile[lane] = f0;
@@ -1245,19 +1441,18 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
   // level 0: one root entry per walking topic
   const unsigned long long bw = __ballot(walk);
   uint32_t wnext = walk ? words.first() : NONE;
-  if (walk && !(D0 && (ix.flags & IX_D0))) {
+  if (walk && !d0) {
     const uint32_t p = lane_prefix(bw);
     L.e[0][p] = make_uint2((!dollar && (ix.root_flags & HOT_PLUS)) ? FR_PLUS : 0u, ix.root_sig);
     L.ln[0][p] = uint8_t(lane);
   }
   uint32_t cur_total = uint32_t(__popcll(bw));
-  const bool hflat = (ix.flags & IX_HOT_FLAT) != 0;
-  const bool d0 = D0 && (ix.flags & IX_D0);  // (wave-uniform)
   uint4 rq = D1_NONE;                       // the root's '+' child {hot id, sig, hf, end}
   if (d0) rq = *reinterpret_cast<const uint4*>(ix.d0_root);
   int cur = 0;
 #ifdef GM_PHASE_STATS
   uint64_t tph = __builtin_amdgcn_s_memtime();
+  const uint64_t tw0 = tph, tr0w = __builtin_amdgcn_s_memrealtime();
 #endif
   // One level of the walk (a lambda, so that level 0 under D0 -- the round
   // from registers -- is its own instance and its extra live values do not
@@ -1275,13 +1470,12 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
     wave_lds_sync();
     const uint32_t lvl = __builtin_amdgcn_readfirstlane(level);
     const int ht = hot_table(lvl + 1);
-    const HotSlot* tab = ix.hot + ix.hot_off[ht];
-    const HotSlot* ptab = ix.hot + ix.hot_off[hot_table(lvl)];  // the frontier nodes' own table
-    const bool hrh = ((ix.rh_mask >> ht) & 1u) != 0;
-    const uint64_t cap = ix.hot_cap[ht];
-    const uint32_t capu = uint32_t(cap);
-    const uint32_t fmask = ix.efilt_mask[ht];
-    const uint32_t* ft = ix.efilt + ix.efilt_off[ht];
+    const LevelTabs<FLAT> LT(ix, ht);
+    // the frontier nodes' own table (their inline '+' children)
+    const TabRef<FLAT> PT(ix.hot + ix.hot_off[hot_table(lvl)], uint32_t(ix.hot_cap[hot_table(lvl)]) * HS);
+    // the probes' cache policy (A/B: GM_L1_BYPASS, GM_HOT_POLICY)
+    uint32_t nol1 = 0u;
+    if constexpr (AB) nol1 = ((ix.l1_bypass >> ht) & 1u) ? ix.hot_policy : 0u;
     const uint2* E = L.e[cur];
     const uint8_t* LNc = L.ln[cur];
     uint2* EN = L.e[cur ^ 1];
@@ -1291,6 +1485,7 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
 #ifdef GM_PHASE_STATS
       const uint64_t tr0 = __builtin_amdgcn_s_memtime();
 #endif
+      GM_PAD();
       // (d0r: level 0 from registers; every walking lane takes its own root entry)
       constexpr bool d0r = D0R;
       const uint32_t e = base + uint32_t(lane);
@@ -1319,39 +1514,38 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
         if (dx) {  // resolve the issued probe; the end filter (a one-level topic) from the found slot
           rx.a = D1L[lane];
           rx.ef = NONE;
-          hx = hot_resolve_x(ix, ht, tab, capu, kx, s1, rx, false, hflat, hrh);
-          if (last && hx != NONE) rx.ef = hot_load(tab, hx, true, hflat).ef;
+          hx = LT.resolve(kx, s1, rx, false);
         }
+        // (a one-level topic: the end filter from the found slot)
+        const uint32_t ef1 = LT.T.template ld32<HS>(hx, 16u, dx && last && hx != NONE, PR_TAIL);
+        if (dx && last && hx != NONE) rx.ef = ef1;
         if (dp) {
           hp = rq.x;
           rp.a = make_uint4(0u, 0u, rq.y, rq.z);
           rp.ef = last ? rq.w : NONE;
         }
       } else {
-      if (const uint32_t mc = ix.mph_cap[ht]) {
+      if (LT.mc) {
         // an MPH table (wave-uniform): one L2 read of the key's bucket word
         // filters the probe and gives its slot, in place of the exact-edge filter
-        if (dx) dx = mph_gate(ix, ht, kx, mc, sx);
-        if (dp && !pin) dp = mph_gate(ix, ht, kp, mc, sp);
+        dx = LT.gate(kx, dx, sx);
+        const bool gp = LT.gate(kp, dp && !pin, sp);
+        dp = pin || gp;
       } else {
-        if (fmask && dx) {  // the table's exact-edge filter (an L2 hit) before a random line
-          const uint32_t fh = edge_filter_hash(kx);
-          const uint32_t fb = edge_filter_bits(fh);
-          dx = (ft[edge_filter_word(fh, fmask)] & fb) == fb;
-        }
-        if (dx) sx = uint32_t(hot_slot(kx, cap));
-        if (dp && !pin) sp = uint32_t(hot_slot(kp, cap));
+        // the table's exact-edge filter (an L2 hit) before a random line
+        if (LT.fmask) dx = LT.filter(kx, dx);
+        sx = uint32_t(hot_slot(kx, LT.cap));
+        sp = uint32_t(hot_slot(kp, LT.cap));
       }
       // issue both probes, then resolve
-      const uint32_t nol1 = ((ix.l1_bypass >> ht) & 1u) ? ix.hot_policy : 0u;
-      if (dx) rx = hot_load(tab, sx, last, hflat, nol1);
-      if (pin) {
-        rp = plus_inline_load(ptab, id, hflat);
-      } else if (dp) {
-        rp = hot_load(tab, sp, last, hflat, nol1);
+      rx = hot_load_t(LT.T, sx, last, dx, nol1);
+      rp = plus_inline_load_t(PT, id, pin);
+      {
+        const HotRec rs = hot_load_t(LT.T, sp, last, dp && !pin, nol1);
+        if (!pin) rp = rs;
       }
-      hx = dx ? hot_resolve_x(ix, ht, tab, capu, kx, sx, rx, last, hflat, hrh) : NONE;
-      hp = pin ? (id | HOT_INLINE) : dp ? hot_resolve_x(ix, ht, tab, capu, kp, sp, rp, last, hflat, hrh) : NONE;
+      hx = dx ? LT.resolve(kx, sx, rx, last) : NONE;
+      hp = pin ? (id | HOT_INLINE) : dp ? LT.resolve(kp, sp, rp, last) : NONE;
       }
 #ifdef GM_PHASE_STATS
       __builtin_amdgcn_s_waitcnt(0);  // (diagnostic build: the probes' data is in)
@@ -1387,8 +1581,8 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
           GM_PHASE_ADD(13, 1);
           const uint32_t w2 = uint32_t(__builtin_amdgcn_ds_bpermute(int(tl) << 2, int(wnext2)));
           uint4 qx{}, qp{};
-          if (tx) qx = hot_tail_load(tab, hx, hflat);
-          if (tp) qp = hot_tail_load(tab, hp, hflat);
+          qx = LT.T.template ld128<HS>(hx, 16u, tx, PR_TAIL);
+          qp = LT.T.template ld128<HS>(hp, 16u, tp, PR_TAIL);
           // the probes the reference NFA makes along the chain (SURVEY §8d's P):
           // c1 found at level+1 (+2 there if it is the topic's last level,
           // else +3 for c1's own frontier entry), c2 found at level+2 alike
@@ -1425,13 +1619,12 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
         const uint32_t ne = uint32_t(e1) + uint32_t(e2) + uint32_t(e3) + uint32_t(e4) + uint32_t(e5) + uint32_t(e6);
         uint32_t rk = ne ? atomicAdd(&MCNT[tl], ne) : 0u;
         const uint32_t tag = uint32_t(tl) << CMP_SHIFT;
-        const bool sc1st = (ix.flags & IX_STAGE_SC1) != 0;
 #define GM_CW_PUT(c, f)                                                                         \
   do {                                                                                          \
     const unsigned long long b_ = __ballot(c);                                                  \
     if (c) {                                                                                    \
       const uint32_t k_ = wbase + lane_prefix(b_);                                              \
-      if (k_ < TCAP) stage_st<NT>(stile, k_, (f) | tag | ((rk < MC ? rk : MC - 1) << CMP_RANK), sc1st); \
+      if (k_ < TCAP) stage_put(k_, (f) | tag | ((rk < MC ? rk : MC - 1) << CMP_RANK), sc1st); \
       ++rk;                                                                                     \
     }                                                                                           \
     wbase += uint32_t(__popcll(b_));                                                            \
@@ -1514,10 +1707,12 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
   const uint32_t m_n = MCNT[lane];
   // CW_OVF or a row past the staging capacity; CMP: the tile's list past its capacity
   const bool ovf = valid && (m_n > MC || (CMP && wbase > TCAP));
+  const __amdgpu_buffer_rsrc_t c8rs = wave_rsrc(SBUF ? cnt8 + tile * 64u : nullptr, SBUF ? 64u : 0u);  // the tile's 64 row bytes
   if (valid) {
     // CMP: one byte per row (0xFF: the listed and slow passes write the row's cnt word)
     if constexpr (CMP) {
-      st_s<NT>(cnt8 + t, uint8_t(ovf ? 0xFFu : m_n));
+      if constexpr (SBUF) __builtin_amdgcn_raw_buffer_store_b8(uint8_t(ovf ? 0xFFu : m_n), c8rs, lane, 0, NT ? 2 : 0);
+      else st_s<NT>(cnt8 + t, uint8_t(ovf ? 0xFFu : m_n));
       // (the listed pass writes its rows' cnt words; until it has run -- it is
       // deferred to the host's read-back, MatchCall::finish -- the row reads
       // as a slow row with no ids, so an assembly before it stays in bounds)
@@ -1527,7 +1722,12 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
     }
     if (ovf) ovf_list[atomicAdd(ovf_n, 1u)] = uint32_t(t);
   }
-  if (CMP && lane == 0) st_s<NT>(tlen + tile, wbase < TCAP ? wbase : TCAP);
+  if constexpr (SBUF) {
+    if (lane == 0)
+      __builtin_amdgcn_raw_buffer_store_b32(wbase < TCAP ? wbase : TCAP, wave_rsrc(tlen + tile, 4u), 0, 0, NT ? 2 : 0);
+  } else if (CMP && lane == 0) {
+    st_s<NT>(tlen + tile, wbase < TCAP ? wbase : TCAP);
+  }
   uint32_t ptot, mtot;
   wave_excl_scan(probes, ptot);
   wave_excl_scan(valid && !ovf ? m_n : 0u, mtot);
@@ -1538,6 +1738,8 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
     if (wb) atomicAdd(wild_ctr, (unsigned long long)__popcll(wb));
   }
 #ifdef GM_PHASE_STATS
+  PH.v[14] = uint32_t(__builtin_amdgcn_s_memtime() - tw0);
+  PH.v[15] = uint32_t(__builtin_amdgcn_s_memrealtime() - tr0w);
   GM_PHASE_ADD(10, __builtin_amdgcn_s_memtime() - tph);
   if (lane == 0 && g_phase_rec)
     for (int k = 0; k < 32; ++k) g_phase_rec[tile * 32 + k] = PH.v[k];
@@ -1558,7 +1760,7 @@ struct WordsFromHbm {  // k_walk_coop: the tokenizer's level-major word ids
   }
 };
 
-template <bool EXACT, bool NT>
+template <bool EXACT, bool NT, bool FLAT>
 __global__ __launch_bounds__(256, 8) void k_walk_coop(const uint8_t* __restrict__ tb,
                                                       const uint64_t* __restrict__ toff, uint64_t n, IndexView ix,
                                                       const uint32_t* __restrict__ hdr,
@@ -1575,8 +1777,8 @@ __global__ __launch_bounds__(256, 8) void k_walk_coop(const uint8_t* __restrict_
   const bool valid = t < n;
   const uint32_t h = valid ? ld_s<NT>(hdr + t) : 0u;
   WordsFromHbm words{wids + (valid ? t : 0), n, NT};
-  coop_walk_tile<EXACT, NT>(s_w[wv], h, words, valid, t, lane, tb, toff, ix, cnt, stage, ovf_list, ovf_n, probe_tile,
-                            wild_ctr, tsum);
+  coop_walk_tile<EXACT, NT, WordsFromHbm, false, false, true, FLAT>(s_w[wv], h, words, valid, t, lane, tb, toff, ix, cnt,
+                                                                    stage, ovf_list, ovf_n, probe_tile, wild_ctr, tsum);
 }
 
 // ---- k_match_fused: tokenize + coop walk in one kernel --------------------
@@ -1600,7 +1802,8 @@ struct WordsFromRegs {
 
 constexpr size_t FUSED_LDS = sizeof(CoopLds) * 4 > (TOK_STAGE + 8) ? sizeof(CoopLds) * 4 : (TOK_STAGE + 8);
 
-template <int G, bool EXACT, bool NT, bool TOKPRIO, bool CMP, bool D0 = true>
+// AB, FLAT: coop_walk_tile's (the default instantiation is AB false, FLAT false)
+template <int G, bool EXACT, bool NT, bool TOKPRIO, bool CMP, bool AB, bool FLAT, bool D0 = true>
 __global__ __launch_bounds__(256, 8) void k_match_fused(const uint8_t* __restrict__ tb,
                                                         const uint64_t* __restrict__ toff, uint64_t n, IndexView ix,
                                                         uint32_t* __restrict__ cnt, uint32_t* __restrict__ stage,
@@ -1645,7 +1848,7 @@ __global__ __launch_bounds__(256, 8) void k_match_fused(const uint8_t* __restric
   if (valid) {
     const uint64_t pos = toff[t], end = toff[t + 1];
     if (staged) {
-      h = tokenize_grouped<G>(s_txt, uint32_t(pos - lo), uint32_t(end - lo), ix, tb + lo, WidsToRegs{w});
+      h = tokenize_grouped<G, !FLAT>(s_txt, uint32_t(pos - lo), uint32_t(end - lo), ix, tb + lo, WidsToRegs{w});
     } else {
       ByteReader rd{tb, ~0ull, 0};
       h = tokenize_topic(rd, pos, end, ix, tb, WidsToRegs{w});
@@ -1661,9 +1864,9 @@ __global__ __launch_bounds__(256, 8) void k_match_fused(const uint8_t* __restric
   // issued before the walk's setup and resolved in its level-0 round (held
   // across the block barrier it spilled)
   D0Probe d1{make_uint4(0u, 0u, 0u, 0u), NONE};
-  if (D0 && (ix.flags & IX_D0)) d1 = d0_issue(ix, w[0], h, valid);
+  if (D0 && (!AB || (ix.flags & IX_D0))) d1 = d0_issue<FLAT>(ix, w[0], h, valid);
   WordsFromRegs words{w};
-  coop_walk_tile<EXACT, NT, WordsFromRegs, CMP, D0>(reinterpret_cast<CoopLds*>(s_raw)[wv], h, words, valid, t, lane,
+  coop_walk_tile<EXACT, NT, WordsFromRegs, CMP, D0, AB, FLAT>(reinterpret_cast<CoopLds*>(s_raw)[wv], h, words, valid, t, lane,
                                                     tb, toff, ix, cnt, stage, ovf_list, ovf_n, probe_tile, wild_ctr,
                                                     tsum, tlen, cnt8, &PH, d1);
 }
@@ -3349,21 +3552,27 @@ void launch_match(emqx_gm_ctx* ctx, const IndexView& v, const uint8_t* tb, const
   hipStream_t st = ctx->stream;
   const uint64_t nblk = (n + 255) / 256;
   *listed_deferred = false;
+  const bool flat = view_flat(v);  // a table too large for 32-bit byte offsets: the flat instantiations
 #define GM_LAUNCH_WALK(W, P, sw, g, base)                                                                        \
   hipLaunchKernelGGL((k_walk<EXACT, W, P>), dim3(g), dim3(256), 0, sw, tb, to, n, v, hdr, wids, cnt, stage, list1, n1, \
                      probe_tile, wild_ctr, tsum, base)
+#define GM_LAUNCH_COOP(NT, FL, sw, g, base)                                                                      \
+  hipLaunchKernelGGL((k_walk_coop<EXACT, NT, FL>), dim3(g), dim3(256), 0, sw, tb, to, n, v, hdr, wids, cnt, stage, list1, \
+                     n1, probe_tile, wild_ctr, tsum, base)
 #define GM_WALK(sw, g, base)                                  \
   do {                                                        \
     switch (main_kind()) {                                    \
       case MAIN_SPLIT: GM_LAUNCH_WALK(1, false, sw, g, base); break;  \
       case MAIN_SPLIT2: GM_LAUNCH_WALK(1, true, sw, g, base); break;  \
       case MAIN_COOP:                                         \
-        if (nt_streams())                                     \
-          hipLaunchKernelGGL((k_walk_coop<EXACT, true>), dim3(g), dim3(256), 0, sw, tb, to, n, v, hdr, wids, cnt, \
-                             stage, list1, n1, probe_tile, wild_ctr, tsum, base);                                 \
+        if (nt_streams() && flat)                             \
+          GM_LAUNCH_COOP(true, true, sw, g, base);            \
+        else if (nt_streams())                                \
+          GM_LAUNCH_COOP(true, false, sw, g, base);           \
+        else if (flat)                                        \
+          GM_LAUNCH_COOP(false, true, sw, g, base);           \
         else                                                  \
-          hipLaunchKernelGGL((k_walk_coop<EXACT, false>), dim3(g), dim3(256), 0, sw, tb, to, n, v, hdr, wids, cnt, \
-                             stage, list1, n1, probe_tile, wild_ctr, tsum, base);                                  \
+          GM_LAUNCH_COOP(false, false, sw, g, base);          \
         break;                                                \
       default: GM_LAUNCH_WALK(8, false, sw, g, base);         \
     }                                                         \
@@ -3392,12 +3601,23 @@ void launch_match(emqx_gm_ctx* ctx, const IndexView& v, const uint8_t* tb, const
     // the kernel's own start / stop timestamps (hipExtLaunchKernel) instead of
     // two event records around it: each record is a barrier packet that costs
     // the stream ~5.5 us of idle GPU (C1 per-call trace, profiles/r03_c1_trace.txt)
-#define GM_FUSED(NT, P, C)                                                                                          \
-  hipExtLaunchKernelGGL((k_match_fused<3, EXACT, NT, P, C>), dim3(nblk), dim3(256), 0, st, kt ? before_main : nullptr,   \
+#define GM_FUSED(NT, P, C)                                             \
+  do {                                                                 \
+    if (flat) GM_FUSED_K(NT, P, C, true, true);                        \
+    else GM_FUSED_K(NT, P, C, true, false);                            \
+  } while (0)
+#define GM_FUSED_K(NT, P, C, AB, FL)                                                                                \
+  hipExtLaunchKernelGGL((k_match_fused<3, EXACT, NT, P, C, AB, FL>), dim3(nblk), dim3(256), 0, st, kt ? before_main : nullptr,   \
                         kt ? after_main : nullptr, 0,                                                                     \
                         tb, to, n, v, cnt, stage, list1, n1, probe_tile, wild_ctr, tsum, tl, c8)
     const bool kt = before_main != nullptr;  // (an untimed call: EMQX_GM_NO_TIMING)
-    if (cb) {
+    // The default instantiation (AB false): default knobs, a view that asks for
+    // no A/B form and buffer-sized tables.  Everything else runs the general one.
+    const bool plain = nt_streams() && tp && !flat && (v.flags & IX_D0) && !(v.flags & IX_STAGE_SC1) && !v.l1_bypass;
+    if (plain) {
+      if (cb) GM_FUSED_K(true, true, true, false, false);
+      else GM_FUSED_K(true, true, false, false, false);
+    } else if (cb) {
       if (nt_streams() && tp) GM_FUSED(true, true, true);
       else if (nt_streams()) GM_FUSED(true, false, true);
       else if (tp) GM_FUSED(false, true, true);
@@ -3410,6 +3630,7 @@ void launch_match(emqx_gm_ctx* ctx, const IndexView& v, const uint8_t* tb, const
       else GM_FUSED(false, false, false);
     }
 #undef GM_FUSED
+#undef GM_FUSED_K
   } else if (K == 1) {
     hipEventRecord(before_main, st);
     launch_tokenize(st, nblk, tb, to, n, v, hdr, wids, 0);
@@ -3431,6 +3652,7 @@ void launch_match(emqx_gm_ctx* ctx, const IndexView& v, const uint8_t* tb, const
     }
   }
 #undef GM_WALK
+#undef GM_LAUNCH_COOP
 #undef GM_LAUNCH_WALK
 #ifdef GM_PROBE_STATS
   {
@@ -3465,7 +3687,8 @@ void launch_match(emqx_gm_ctx* ctx, const IndexView& v, const uint8_t* tb, const
         if (rounds[l] > 0)
           fprintf(stderr, " L%d %.0f (%.2f rounds: to data %.0f, rest %.0f)", l, sum[2 + l] / w, rounds[l] / w,
                   sum[16 + l] / w, sum[24 + l] / w);
-      fprintf(stderr, " epi %.0f; chain-tail rounds/wave %.2f\n", sum[10] / w, sum[13] / w);
+      fprintf(stderr, " epi %.0f; chain-tail rounds/wave %.2f; walk %.0f memtime / %.0f memrealtime ticks = %.1f MHz\n",
+              sum[10] / w, sum[13] / w, sum[14] / w, sum[15] / w, sum[15] > 0 ? sum[14] / sum[15] * 100.0 : 0.0);
     }
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_phase_rec), &null_rec, sizeof null_rec);
     (void)hipFree(phase_rec);
@@ -3710,6 +3933,7 @@ int MatchCall::submit(const emqx_gm_index* index, const uint8_t* tb_in, const ui
     if (atoi(se)) vcall.flags |= IX_STAGE_SC1;
   if (const char* be = knob("GM_L1_BYPASS")) vcall.l1_bypass = uint32_t(strtoul(be, nullptr, 0));
   if (const char* pe = knob("GM_HOT_POLICY")) vcall.hot_policy = uint32_t(strtoul(pe, nullptr, 0));
+  if (knob("GM_HOT_FLAT")) vcall.flags |= IX_HOT_FLAT;  // (test knob, also read per call: the flat instantiation)
   if (exact)
     launch_match<true>(ctx, vcall, tb, to, n, cnt.as<uint32_t>(), stage.as<uint32_t>(), list1.as<uint32_t>(), n1,
                        list2.as<uint32_t>(), n2, probe_ctr, wild_ctr, hdr.as<uint32_t>(), wids.as<uint32_t>(),

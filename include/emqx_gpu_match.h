@@ -63,7 +63,8 @@
  *   walk and staging:   GM_MATCH_MAIN (the superseded split / coop / lds
  *     forms), GM_TOK_GROUP, GM_OVERLAP, GM_FUSED_PRIO, GM_HOT_POLICY, GM_NT,
  *     GM_D0, GM_STAGE_COMPACT, GM_STAGE_SC1, GM_LISTED_CAP, GM_LISTED_DEFER,
- *     GM_SCAN_SPLIT, GM_SCAN_SUMS, GM_NO_SPEC_IDS, GM_ASM_STREAM;
+ *     GM_SCAN_SPLIT, GM_SCAN_SUMS, GM_NO_SPEC_IDS, GM_ASM_STREAM, GM_HOT_FLAT
+ *     (per call too: the walk's flat-load instantiation);
  *   host path:          GM_HOST_SIMPLE, GM_HOST_PIPE, GM_HOST_CHUNK,
  *     GM_HOST_THREADS, GM_HOST_BOUNCE, GM_HOST_WIDE_ROWS, GM_HOST_OFF32,
  *     GM_FANOUT_MULTI_MIN, GM_FANOUT_SIMPLE, GM_FANOUT_FUSED_ONLY;
