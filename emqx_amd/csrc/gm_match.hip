@@ -602,6 +602,7 @@ __global__ __launch_bounds__(256) void k_match_lds(const uint8_t* __restrict__ t
     }
     if (wild) {
       GM_WILD_ROW();
+      tprobes = 0;  // a wildcard publish topic is not walked: P = 0, as the main passes count it
     } else if (!ovf) {
       tprobes += 2 * nfinal + 1;
       if (m_n > MC) ovf = true;
@@ -615,7 +616,8 @@ __global__ __launch_bounds__(256) void k_match_lds(const uint8_t* __restrict__ t
     if (ovf) ovf_list[atomicAdd(ovf_n, 1u)] = uint32_t(t);
     else if (LISTED) atomicAdd(reinterpret_cast<unsigned long long*>(tsum + tile), (unsigned long long)m_n);
     probes += tprobes;
-    wilds += wild ? 1u : 0u;
+    // (a listed wildcard topic -- one deeper than TOK_LMAX -- is already in wild_ctr: the main pass counted it)
+    wilds += !LISTED && wild ? 1u : 0u;
     if (!LISTED) break;
   }
   // per-wave counters (one atomic per wave)
@@ -4081,7 +4083,7 @@ int MatchCall::finish(emqx_gm_csr* out, MatchTail* tail, bool locked) {
   }
   S.probes = h_ctr[2];
   S.n_wildcard_topics = h_ctr[3];
-  S.n_overflow = uint32_t(h_ctr[0]);
+  S.n_overflow = uint32_t(h_ctr[0] >> 32);  // n2: the rows the slow path completes (the low half, n1, is the listed queue)
   if (spec && uint32_t(h_ctr[0] >> 32) == 0 && nnz <= cap_spec) {  // no slow-path row, and the rows fit: done
     ctx->ids_per_topic = std::max(1.0, 1.25 * double(nnz) / double(n));
     S.nnz = nnz;

@@ -186,15 +186,24 @@ typedef struct {
   int32_t trie_empty;    /* emqx_trie:empty/0 (no wildcard filter)              */
 } emqx_gm_index_info_t;
 
+/* probes: the probes the reference NFA makes for the batch (SURVEY.md 8d's P),
+ * not a count of loads: per topic 1 (the exact-route probe) + 3 per frontier
+ * node and level + 2 per node reached at the last level; 0 for a wildcard
+ * publish topic.  Exact when no row leaves a pass for capacity (a row of more
+ * than 16 matches, a frontier past a pass's capacity, a full tile list);
+ * otherwise each such row may be counted by up to two passes: the main pass
+ * and the listed pass each add what they walked of it before giving it up, the
+ * slow path adds nothing.  Topics of more than 8 levels are counted by the
+ * listed pass alone.  (tests/test_gpu_probe_count.py) */
 typedef struct {
   uint64_t n_topics;
   uint64_t nnz;
   uint64_t n_overflow;       /* rows completed by the device slow path        */
-  uint64_t n_wildcard_topics;
+  uint64_t n_wildcard_topics; /* publish topics with a '+' or '#' word (each once) */
   double match_kernel_ms;    /* device time of the fast match kernel          */
   double total_device_ms;    /* device time of all kernels of the call         */
   uint64_t algo_bytes;       /* algorithmic bytes of the fast kernel */
-  uint64_t probes;           /* NFA edge probes counted by the fast kernel     */
+  uint64_t probes;           /* NFA edge probes of the batch (see above)       */
 } emqx_gm_match_stats;
 
 /* ---- context ---- */

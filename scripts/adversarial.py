@@ -63,7 +63,7 @@ for D in [int(x) for x in (sys.argv[1:] or ["6", "9", "12"])]:
     best = min(ts)
     print(json.dumps({"depth": D, "filters": len(filters), "topics": N, "ms": best * 1e3,
                       "topics_per_s": N / best, "matches_per_topic": nnz / N, "kernel_ms": st["match_kernel_ms"],
-                      "device_ms": st["total_device_ms"], "listed_rows": st["n_overflow"],
+                      "device_ms": st["total_device_ms"], "slow_rows": st["n_overflow"],
                       "oracle_sample_ok": ok}), flush=True)
     ctx.dev_free(d_b)
     ctx.dev_free(d_o)

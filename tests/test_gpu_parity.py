@@ -589,7 +589,10 @@ def test_tokenizer_groups(ctx, orc, monkeypatch, group):
     """k_tokenize<G> (GM_TOK_GROUP, words resolved G levels at a time): the
     group boundary against wildcard words, '$' first words, empty levels,
     trailing '/', and topics deeper than the 8 tokenized levels must give
-    the same rows as the oracle for every G."""
+    the same rows as the oracle for every G.  k_tokenize runs only under the
+    split main passes (the default fused kernel tokenizes into registers, always
+    three levels at a time), so every G is run under GM_MATCH_MAIN=coop
+    (k_walk_coop) and splitw8 (k_walk), and under the default as before."""
     monkeypatch.setenv("GM_TOK_GROUP", group)
     rng = random.Random(23)
     words = [b"a", b"b", b"", b"cc", b"longword_over_8_bytes", b"$SYS", b"d"]
@@ -607,8 +610,11 @@ def test_tokenizer_groups(ctx, orc, monkeypatch, group):
         if rng.random() < 0.1:  # a wildcard word at any level, including past the group / 8-level bounds
             lev[rng.randrange(n)] = rng.choice([b"+", b"#"])
         topics.append(b"/".join(lev))
-    _check(ctx, orc, sorted(filters), topics, True)
-    _check(ctx, orc, filters, topics, False)
+    for main in (None, "coop", "splitw8"):
+        if main:
+            monkeypatch.setenv("GM_MATCH_MAIN", main)
+        _check(ctx, orc, sorted(filters), topics, True)
+        _check(ctx, orc, filters, topics, False)
 
 
 @pytest.mark.gpu
@@ -617,8 +623,13 @@ def test_overlapped_match_equals_single_launch(ctx, orc, monkeypatch, chunks):
     """GM_OVERLAP=K (tokenizer of chunk i on a second stream while the walk of
     chunk i-1 runs): the CSR must be bit-identical to the one-launch result
     (itself checked against the oracle above), and a strided sample of rows
-    must equal the oracle's."""
+    must equal the oracle's.  The knob is read by the split main passes only:
+    the test runs k_tokenize + k_walk_coop (GM_MATCH_MAIN=coop), and the host
+    batch as one chunk (the default 256K-topic chunks are 1,024 blocks each,
+    under the K * 1,024 blocks the chunked launch needs)."""
     from emqx_amd.engine import gen_filter_codes, render_codes
+    monkeypatch.setenv("GM_MATCH_MAIN", "coop")
+    monkeypatch.setenv("GM_HOST_CHUNK", "4194304")
     codes = gen_filter_codes(3, 20000, wildcard_only=True)
     fb, fo = render_codes(codes)
     filters = orc.unpack(fb, fo)
