@@ -1784,7 +1784,9 @@ __global__ __launch_bounds__(256, 8) void k_walk_coop(const uint8_t* __restrict_
 }
 
 // ---- k_match_fused: tokenize + coop walk in one kernel --------------------
-// The block stages its topics' text in LDS and each lane tokenizes its topic
+// The block stages its topics' text in LDS (stage_text: the offsets' loads
+// issued together at entry, then every text load in flight before the first
+// LDS write) and each lane tokenizes its topic
 // into REGISTERS (word ids of up to TOK_LMAX levels, the header); then each
 // wave walks its tile as k_walk_coop does, in the same LDS.  The word ids
 // and headers never go through HBM (k_tokenize + k_walk_coop write and read
@@ -1804,6 +1806,58 @@ struct WordsFromRegs {
 
 constexpr size_t FUSED_LDS = sizeof(CoopLds) * 4 > (TOK_STAGE + 8) ? sizeof(CoopLds) * 4 : (TOK_STAGE + 8);
 
+// Two uniform 8-byte loads issued together, one wait for both (left to the
+// compiler, the first is waited for before the second is issued: one more
+// round trip at the head of every block)
+__device__ __forceinline__ void ld_uniform_pair(const uint64_t* p0, const uint64_t* p1, uint64_t& a, uint64_t& b) {
+  asm volatile("s_load_dwordx2 %0, %2, 0x0\n\ts_load_dwordx2 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(a), "=&s"(b)
+               : "s"(p0), "s"(p1)
+               : "memory");
+}
+
+// Text staging with every load in flight before the first LDS write: bytes
+// [0, r8) of src (8-byte aligned; r8 a multiple of 8, at most CAP) go to dst,
+// 16 bytes per lane and trip, W lanes (id < W) sharing the copy.  The loads go
+// through a buffer resource of the text's own size (rounded up to the 16-byte
+// access: at most 8 bytes past r8), so a lane past the text issues its load
+// like the others and the range check drops it -- no branch around a load, no
+// wait between two of them.  The first FIRST trips cover the common text; a
+// longer one takes the rest of the trips under one uniform branch.  LDS
+// writes are bounded by r8 word by word (dst holds r8 bytes, not the rounding).
+template <int W, int CAP, bool NT, int FIRST = 2>
+__device__ __forceinline__ void stage_text(uint64_t* dst, const uint8_t* src, uint32_t r8, uint32_t id) {
+  constexpr int TRIP = 16 * W, TRIPS = (CAP + TRIP - 1) / TRIP, T0 = FIRST < TRIPS ? FIRST : TRIPS;
+  const uint64_t a = reinterpret_cast<uint64_t>(src);
+  const uint64_t u = (uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(a >> 32)))) << 32) |
+                     uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(a))));
+  const __amdgpu_buffer_rsrc_t rs =
+      __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(u), (short)0, int((r8 + 15u) & ~15u), 0x00020000);
+  const uint32_t o = id * 16u;
+  auto ld = [&](int k) { return __builtin_amdgcn_raw_buffer_load_b128(rs, int(o + uint32_t(k * TRIP)), 0, NT ? 2 : 0); };
+  auto put = [&](int k, const auto& v) {
+    const uint32_t b = o + uint32_t(k * TRIP);
+    if (b < r8) dst[b >> 3] = (uint64_t(uint32_t(v[1])) << 32) | uint32_t(v[0]);
+    if (b + 8u < r8) dst[(b >> 3) + 1] = (uint64_t(uint32_t(v[3])) << 32) | uint32_t(v[2]);
+  };
+  {
+    decltype(ld(0)) v[T0];
+#pragma unroll
+    for (int k = 0; k < T0; ++k) v[k] = ld(k);
+#pragma unroll
+    for (int k = 0; k < T0; ++k) put(k, v[k]);
+  }
+  if constexpr (TRIPS > T0) {
+    if (r8 > uint32_t(T0 * TRIP)) {  // uniform
+      decltype(ld(0)) v[TRIPS - T0];
+#pragma unroll
+      for (int k = T0; k < TRIPS; ++k) v[k - T0] = ld(k);
+#pragma unroll
+      for (int k = T0; k < TRIPS; ++k) put(k, v[k - T0]);
+    }
+  }
+}
+
 // AB, FLAT: coop_walk_tile's (the default instantiation is AB false, FLAT false)
 template <int G, bool EXACT, bool NT, bool TOKPRIO, bool CMP, bool AB, bool FLAT, bool D0 = true>
 __global__ __launch_bounds__(256, 8) void k_match_fused(const uint8_t* __restrict__ tb,
@@ -1816,7 +1870,8 @@ __global__ __launch_bounds__(256, 8) void k_match_fused(const uint8_t* __restric
                                                         uint8_t* __restrict__ cnt8) {
   __shared__ __align__(16) uint8_t s_raw[FUSED_LDS];  // the staged text, then the walk's lists
   uint64_t* const s_txt = reinterpret_cast<uint64_t*>(s_raw);
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // (wv through readfirstlane: the tile's base and the wave's slice are scalar values, not VGPRs)
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   // TOKPRIO: staging and tokenizing at wave priority 1, the walk at 0.  A block
   // holds its 20 KB of LDS (one of the CU's 8 block slots) through both phases
   // but only the walk keeps lines in flight, so the SIMD's issue arbiter favours
@@ -1828,27 +1883,32 @@ __global__ __launch_bounds__(256, 8) void k_match_fused(const uint8_t* __restric
   const uint64_t tp0 = __builtin_amdgcn_s_memtime();
 #endif
   const uint64_t t0 = uint64_t(blockIdx.x) * 256u;
-  const uint64_t t = t0 + threadIdx.x;
+  const uint64_t tw = t0 + uint32_t(wv) * 64u;  // the wave's first topic
+  const uint64_t t = tw | uint32_t(lane);
+  const bool valid = t < n;
+  // the lane's own offsets, issued first (a lane past n reads the last
+  // topic's: toff has n + 1 entries)
+  const uint64_t tc = valid ? t : n - 1;
+  const uint64_t pos = toff[tc], end = toff[tc + 1];
+  // the block's text [lo, hi): both bounding offsets in one round trip
   const uint64_t tl = t0 + 256 < n ? t0 + 256 : n;
-  const uint64_t lo = toff[t0] & ~7ull, hi = toff[tl];
+  uint64_t lo, hi;
+  ld_uniform_pair(toff + t0, toff + tl, lo, hi);
+  lo &= ~7ull;
   const bool staged = hi - lo <= uint64_t(TOK_STAGE) - 8;  // block-uniform
-  if (staged) {
-    const uint64_t nw = ((hi - lo + 7) >> 3) + 1;  // topic buffers are padded by 64 bytes
-    for (uint64_t i = threadIdx.x; i < nw; i += 256) s_txt[i] = ld_s<NT>(reinterpret_cast<const uint64_t*>(tb + lo + 8 * i));
-  }
+  // (one word past the text for the funnel shifts: topic buffers are padded by 64 bytes)
+  if (staged) stage_text<256, TOK_STAGE, NT>(s_txt, tb + lo, uint32_t(((hi - lo + 7) & ~7ull) + 8), threadIdx.x);
   __syncthreads();
   PhaseRec PH{};
 #ifdef GM_PHASE_STATS
   const uint64_t tp1 = __builtin_amdgcn_s_memtime();
   PH.v[0] = uint32_t(tp1 - tp0);
 #endif
-  const bool valid = t < n;
   uint32_t w[TOK_LMAX];
 #pragma unroll
   for (int q = 0; q < TOK_LMAX; ++q) w[q] = NONE;
   uint32_t h = 0;
   if (valid) {
-    const uint64_t pos = toff[t], end = toff[t + 1];
     if (staged) {
       h = tokenize_grouped<G, !FLAT>(s_txt, uint32_t(pos - lo), uint32_t(end - lo), ix, tb + lo, WidsToRegs{w});
     } else {
@@ -1868,7 +1928,13 @@ __global__ __launch_bounds__(256, 8) void k_match_fused(const uint8_t* __restric
   D0Probe d1{make_uint4(0u, 0u, 0u, 0u), NONE};
   if (D0 && (!AB || (ix.flags & IX_D0))) d1 = d0_issue<FLAT>(ix, w[0], h, valid);
   WordsFromRegs words{w};
-  coop_walk_tile<EXACT, NT, WordsFromRegs, CMP, D0, AB, FLAT>(reinterpret_cast<CoopLds*>(s_raw)[wv], h, words, valid, t, lane,
+  // the walk's topic index, formed again from the wave's scalar base (hidden
+  // from value numbering) so that the front end's copy is not held in two
+  // VGPRs through the tokenizer
+  uint32_t twl = uint32_t(tw), twh = uint32_t(tw >> 32);
+  asm volatile("" : "+s"(twl), "+s"(twh));
+  const uint64_t t_w = (uint64_t(twh) << 32) | (twl | uint32_t(lane));
+  coop_walk_tile<EXACT, NT, WordsFromRegs, CMP, D0, AB, FLAT>(reinterpret_cast<CoopLds*>(s_raw)[wv], h, words, valid, t_w, lane,
                                                     tb, toff, ix, cnt, stage, ovf_list, ovf_n, probe_tile, wild_ctr,
                                                     tsum, tlen, cnt8, &PH, d1);
 }
