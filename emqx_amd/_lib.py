@@ -17,6 +17,7 @@ OK, EINVAL, ENOMEM, EDEVICE, EOVERFLOW, EUNSUPPORTED = 0, -1, -2, -3, -4, -5
 WITH_EXACT = 0x1
 DEVICE_IO = 0x2
 NO_TIMING = 0x4
+RET_TIMED = 0x1
 OPEN_MIRROR_EAGER = 0x1
 OPEN_MIRROR_LAZY = 0x2
 IMAGE_NO_BLOB = 0x1
@@ -62,6 +63,12 @@ class UpdateStats(C.Structure):
                 ("mirror_loaded", C.c_int32), ("mirror_bytes", C.c_uint64), ("mirror_ms", C.c_double),
                 ("device_ms", C.c_double), ("replicate_ms", C.c_double), ("total_ms", C.c_double),
                 ("blobs_reused", C.c_uint32), ("blobs_fresh", C.c_uint32)]
+
+
+class RetainedInfo(C.Structure):
+    _fields_ = [("n_topics", C.c_uint64), ("n_nodes", C.c_uint64), ("n_words", C.c_uint64),
+                ("device_bytes", C.c_uint64), ("widest_level", C.c_uint64), ("walk_ws_bytes", C.c_uint64),
+                ("depth_max", C.c_uint32), ("lds_frames", C.c_int32)]
 
 
 UPD_KINDS = {0: "none", 1: "patch", 2: "overlay", 3: "rebuild", 4: "subs_only", 5: "build", 6: "import", 7: "shift"}
@@ -112,6 +119,11 @@ SIGNATURES = {
     "emqx_gm_route_partition": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "emqx_gm_permute_topics": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "emqx_gm_unpermute_rows": (_i32, [_vp, _u64, _vp, _vp, _vp, _u32, C.POINTER(Csr)]),
+    "emqx_gm_retained_build": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u32, C.POINTER(_vp)]),
+    "emqx_gm_retained_match": (_i32, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, C.POINTER(Csr)]),
+    "emqx_gm_retained_expire": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
+    "emqx_gm_retained_info": (_i32, [_vp, C.POINTER(RetainedInfo)]),
+    "emqx_gm_retained_release": (_i32, [_vp]),
     # emqx_gm_ext.h
     "emqx_gm_gen_filter_codes": (_i32, [_u64, _u64, _i32, _vp]),
     "emqx_gm_render_codes": (_u64, [_vp, _u64, _vp, _vp]),
@@ -129,6 +141,10 @@ SIGNATURES = {
     "emqx_gm_index_replica_digest": (_i32, [_vp, _vp, _u32, C.POINTER(_u64), C.POINTER(_u64)]),
     "emqx_gm_last_shard_update": (_i32, [_vp, _vp, C.POINTER(_u32)]),
     "emqx_gm_route_filter_shards_host": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "emqx_gm_retained_compile_host": (_i32, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_vp)]),
+    "emqx_gm_retained_match_host": (_i32, [_vp, _vp, _vp, _u64, _u64, C.POINTER(Csr)]),
+    "emqx_gm_retained_csr_free_host": (_i32, [C.POINTER(Csr)]),
+    "emqx_gm_retained_last_times": (_i32, [_vp, C.POINTER(C.c_double)]),
 }
 
 _LIB = None

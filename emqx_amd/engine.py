@@ -368,6 +368,13 @@ class Context:
                                               C.byref(h)), self.h, "index_update_subs")
         return Index(self, h, np.zeros(0, np.uint32))
 
+    def build_retained(self, topics, ids=None, expiry_ms=None):
+        """A retained-topic index over ``topics`` (emqx_gm_retained_build): the
+        subscribe direction, see :mod:`emqx_amd.retainer`.  ``ids``: the caller's
+        id per topic (default: its position); ``expiry_ms``: per topic, 0 = never."""
+        from .retainer import build_retained
+        return build_retained(self, topics, ids, expiry_ms)
+
     # ------------------------------------------------------------------ match
     def match(self, index: Index, topics, exact: bool = True) -> Tuple[np.ndarray, np.ndarray]:
         """Batch emqx_router:match_routes/1 (exact=True) or emqx_trie:match/1

@@ -124,6 +124,20 @@ int emqx_gm_route_filter_shards_host(const emqx_gm_route *route, const uint8_t *
 int emqx_gm_index_replica_digest(emqx_gm_ctx *ctx, const emqx_gm_index *idx, uint32_t k, uint64_t *tables,
                                  uint64_t *subs);
 
+/* Test and measurement support for the retained-topic index (no product path
+ * uses these).  compile_host: the index compiled on the host alone (no device,
+ * no context); emqx_gm_retained_match and _expire refuse it.  match_host: the
+ * walk of emqx_gm_retained_match over the host copy of the tables, single
+ * threaded, no device call; the CSR is malloc'd (free with
+ * emqx_gm_retained_csr_free_host).  last_times: device ms of the count pass,
+ * the scan and the fill pass of the index's last EMQX_GM_RET_TIMED match. */
+int emqx_gm_retained_compile_host(const uint8_t *topic_bytes, const uint64_t *topic_off, uint64_t n_topics,
+                                  const uint32_t *ids, const uint64_t *expiry_ms, emqx_gm_retained **out);
+int emqx_gm_retained_match_host(const emqx_gm_retained *idx, const uint8_t *filter_bytes,
+                                const uint64_t *filter_off, uint64_t n_filters, uint64_t now_ms, emqx_gm_csr *out);
+int emqx_gm_retained_csr_free_host(emqx_gm_csr *csr);
+int emqx_gm_retained_last_times(const emqx_gm_retained *idx, double *ms3);
+
 #ifdef __cplusplus
 }
 #endif

@@ -452,6 +452,70 @@ int emqx_gm_permute_topics(emqx_gm_ctx *ctx, const uint8_t *d_topic_bytes, const
 int emqx_gm_unpermute_rows(emqx_gm_ctx *ctx, uint64_t n_rows, const uint32_t *d_perm, const uint32_t *d_lens,
                            const uint32_t *d_ids, uint32_t flags, emqx_gm_csr *out);
 
+/* ---- retained-message lookup (gm_retained.cpp / gm_retained.hip): the subscribe direction ----
+ * When a client subscribes, the broker hands it every retained message whose
+ * topic the filter matches.  The reference scans the whole table per
+ * subscription: emqx_retainer_mnesia:match_messages/1 turns the filter into a
+ * match-spec (condition/1) and runs mnesia:dirty_select over it
+ * (apps/emqx_retainer/src/emqx_retainer_mnesia.erl:210-244).  Here the stored
+ * topics are compiled once into a level trie in HBM and a batch of filters is
+ * walked against it, one wave per filter.
+ * Semantics (bit-exact with condition/1, emqx_retainer_mnesia.erl:225-230): topics
+ * and filters are split on '/', empty words kept; '+' matches any one word; a
+ * final '#' matches any number of further words, none included ('a/#' matches
+ * 'a'); without it the word counts must be equal; a '#' before the last word
+ * matches nothing (the row is empty, the call does not fail); 'a+' is a
+ * literal.  There is NO '$'-rule: '#' and '+/x' match '$SYS/...' topics, unlike
+ * emqx_gm_match.  A topic is returned if its expiry is 0 or > now_ms
+ * (make_match_spec/1, :232-244); the library reads no clock.
+ * A result row holds the caller's ids of the matching topics in word-list order
+ * of the topics (word by word as unsigned bytes, a proper prefix first); the
+ * reference's sort by timestamp (sort_retained/1) is the caller's.
+ * On a multi-device context the index lives on the first listed device and the
+ * calls run there (no replication). */
+typedef struct emqx_gm_retained emqx_gm_retained;
+typedef struct {
+  uint64_t n_topics;      /* distinct stored topics                              */
+  uint64_t n_nodes;       /* level-trie nodes, root and sentinels included       */
+  uint64_t n_words;       /* distinct words                                      */
+  uint64_t device_bytes;  /* resident index bytes in HBM (0: a host-only index)  */
+  uint64_t widest_level;  /* nodes of the widest level                           */
+  uint64_t walk_ws_bytes; /* global workspace a match call takes (0: LDS frames) */
+  uint32_t depth_max;     /* words of the deepest topic                          */
+  int32_t lds_frames;     /* 1: the walk's frames fit LDS, 0: global workspace   */
+} emqx_gm_retained_info_t;
+/* The table as emqx_retainer_mnesia:store_retained/2 leaves it (:74-104; mria:
+ * dirty_write overwrites): duplicates allowed, the LAST one's id and expiry
+ * are kept.  ids NULL: the position in the input; expiry_ms NULL: none expires.
+ * flags: 0.  n_topics < 2^32 - 1; offsets must ascend and each topic be under
+ * 2 GiB -- the boundary carries no byte count, so that is how far an offset
+ * past the buffer can be told (EMQX_GM_EINVAL, before any device work). */
+int emqx_gm_retained_build(emqx_gm_ctx *ctx, const uint8_t *topic_bytes, const uint64_t *topic_off,
+                           uint64_t n_topics, const uint32_t *ids, const uint64_t *expiry_ms, uint32_t flags,
+                           emqx_gm_retained **out);
+/* emqx_retainer_mnesia:match_messages/1 (:210-214) batched over n_filters
+ * subscriptions: host buffers in, a host CSR out exactly as the host-buffer
+ * emqx_gm_match returns one (free with emqx_gm_csr_free).  flags: 0, or
+ * EMQX_GM_RET_TIMED (the call's passes are timed, emqx_gm_retained_last_times). */
+#define EMQX_GM_RET_TIMED 0x1u
+int emqx_gm_retained_match(emqx_gm_ctx *ctx, const emqx_gm_retained *idx, const uint8_t *filter_bytes,
+                           const uint64_t *filter_off, uint64_t n_filters, uint64_t now_ms, uint32_t flags,
+                           emqx_gm_csr *out);
+/* Sets the expiry of the stored topics among n_topics literal topics (absent
+ * ones are skipped); *n_found = the stored ones.  NOT a snapshot: the expiry
+ * array is mutated in place, in stream order with matches.  Covers
+ * emqx_retainer_mnesia:delete_message/2 of a literal topic (:117-128: set
+ * expiry 1), a refreshed message on an existing topic (store_retained/2), and
+ * clear_expired/1 (:106-115), which needs no call: a match already hides expired
+ * topics.  A topic listed twice in one call gets one of its expiries. */
+int emqx_gm_retained_expire(emqx_gm_ctx *ctx, emqx_gm_retained *idx, const uint8_t *topic_bytes,
+                            const uint64_t *topic_off, uint64_t n_topics, const uint64_t *expiry_ms,
+                            uint64_t *n_found);
+/* emqx_retainer_mnesia:size/1 (:164-165) and the table's shape */
+int emqx_gm_retained_info(const emqx_gm_retained *idx, emqx_gm_retained_info_t *info);
+/* emqx_retainer_mnesia:clean/1 of this table (:160-162) */
+int emqx_gm_retained_release(emqx_gm_retained *idx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@
 
 -export([load_index/1, load_index/2, load_index_sharded/1, load_index_sharded/2, update_index/2, update_subs/2,
          match_batch/2, match_routes_batch/2, fanout_batch/2, empty/1, export_index/1, import_index/1]).
+-export([load_retained/1, load_retained/2, match_retained/3, expire_retained/2]).
 -export([match/2]).
 
 -on_load(init/0).
@@ -88,6 +89,28 @@ export_index(_Index) -> erlang:nif_error(nif_not_loaded).
 %% (another library build) is {error, _}.
 -spec import_index(binary()) -> {ok, reference()} | {error, term()}.
 import_index(_Image) -> erlang:nif_error(nif_not_loaded).
+
+%% The retained-message table (emqx_retainer_mnesia.erl:74-104) as an index in
+%% HBM: the subscribe direction.  Ids in match_retained/3 rows are positions in
+%% Topics (of equal topics the last one); ExpiryMs 0 = never.  On a node with
+%% several GPUs the table lives on the first one.
+-spec load_retained([binary()]) -> {ok, reference()} | {error, term()}.
+load_retained(_Topics) -> erlang:nif_error(nif_not_loaded).
+
+-spec load_retained([binary()], [non_neg_integer()]) -> {ok, reference()} | {error, term()}.
+load_retained(_Topics, _ExpiryMs) -> erlang:nif_error(nif_not_loaded).
+
+%% emqx_retainer_mnesia:match_messages/1 (:210-214) per filter: the ids of the
+%% stored topics it matches whose expiry is 0 or > NowMs, in topic order.  No
+%% '$'-rule: <<"#">> returns <<"$SYS/...">> topics, as condition/1 does.
+-spec match_retained(reference(), [binary()], non_neg_integer()) -> [[non_neg_integer()]] | {error, term()}.
+match_retained(_Index, _Filters, _NowMs) -> erlang:nif_error(nif_not_loaded).
+
+%% Set the expiry of stored topics in place: {Topic, 1} is delete_message/2 of
+%% a literal topic (:117-128), {Topic, ExpiryMs} a refreshed message.  Returns
+%% how many of the topics were stored.
+-spec expire_retained(reference(), [{binary(), non_neg_integer()}]) -> {ok, non_neg_integer()} | {error, term()}.
+expire_retained(_Index, _TopicExpiries) -> erlang:nif_error(nif_not_loaded).
 
 %% emqx_trie:match/1 drop-in with fallback.
 -spec match(reference(), binary()) -> [binary()].

@@ -26,7 +26,11 @@ typedef struct {
   emqx_gm_index *idx;
 } gm_index_res;
 
-static ErlNifResourceType *INDEX_RT;
+typedef struct {
+  emqx_gm_retained *idx;
+} gm_retained_res;
+
+static ErlNifResourceType *INDEX_RT, *RETAINED_RT;
 static emqx_gm_ctx *CTX;
 static ERL_NIF_TERM A_OK, A_ERROR, A_BADARG, A_INSERT, A_DELETE, A_SUBSCRIBE, A_UNSUBSCRIBE, A_ROUTE_ADD,
     A_ROUTE_DELETE;
@@ -35,6 +39,12 @@ static void index_dtor(ErlNifEnv *env, void *obj) {
   gm_index_res *r = (gm_index_res *)obj;
   (void)env;
   if (r->idx) emqx_gm_index_release(r->idx);
+}
+
+static void retained_dtor(ErlNifEnv *env, void *obj) {
+  gm_retained_res *r = (gm_retained_res *)obj;
+  (void)env;
+  if (r->idx) emqx_gm_retained_release(r->idx);
 }
 
 /* LoadInfo (erlang:load_nif/2): a device ordinal, or the node's device list
@@ -61,6 +71,7 @@ static int load(ErlNifEnv *env, void **priv, ERL_NIF_TERM info) {
     o.device = device;
   }
   INDEX_RT = enif_open_resource_type(env, NULL, "emqx_gm_index", index_dtor, ERL_NIF_RT_CREATE, NULL);
+  RETAINED_RT = enif_open_resource_type(env, NULL, "emqx_gm_retained", retained_dtor, ERL_NIF_RT_CREATE, NULL);
   A_OK = enif_make_atom(env, "ok");
   A_ERROR = enif_make_atom(env, "error");
   A_BADARG = enif_make_atom(env, "badarg");
@@ -70,7 +81,7 @@ static int load(ErlNifEnv *env, void **priv, ERL_NIF_TERM info) {
   A_UNSUBSCRIBE = enif_make_atom(env, "unsubscribe");
   A_ROUTE_ADD = enif_make_atom(env, "route_add");
   A_ROUTE_DELETE = enif_make_atom(env, "route_delete");
-  return emqx_gm_open(&o, &CTX) == EMQX_GM_OK && INDEX_RT ? 0 : 1;
+  return emqx_gm_open(&o, &CTX) == EMQX_GM_OK && INDEX_RT && RETAINED_RT ? 0 : 1;
 }
 
 static void unload(ErlNifEnv *env, void *priv) {
@@ -485,6 +496,128 @@ static ERL_NIF_TERM import_index(ErlNifEnv *env, int argc, const ERL_NIF_TERM ar
   return make_index_term(env, idx);
 }
 
+/* ---- retained-message lookup (emqx_gm_retained_*): the emqx_retainer backend's table ----
+ * NowMs and expiries are milliseconds since the epoch: past 32 bits, read with
+ * enif_get_ulong (64-bit on the platforms this library runs on). */
+#ifdef EMQX_TEST_ERL_NIF_STUB_H /* the syntax-check stub lists only what the shim used before; the real header has it */
+int enif_get_ulong(ErlNifEnv *, ERL_NIF_TERM, unsigned long *);
+#endif
+
+static ERL_NIF_TERM make_retained_term(ErlNifEnv *env, emqx_gm_retained *idx) {
+  gm_retained_res *r = enif_alloc_resource(RETAINED_RT, sizeof(*r));
+  ERL_NIF_TERM term;
+  r->idx = idx;
+  term = enif_make_resource(env, r);
+  enif_release_resource(r);
+  return enif_make_tuple2(env, A_OK, term);
+}
+
+/* load_retained([Topic]) | load_retained([Topic], [ExpiryMs]) -> {ok, Index}
+ * the table store_retained/2 maintains (emqx_retainer_mnesia.erl:74-104); ids
+ * in match_retained/3 rows are positions in [Topic] (of equal topics the last) */
+static ERL_NIF_TERM load_retained(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  uint8_t *tb;
+  uint64_t *to, n, i = 0, *ex = NULL;
+  emqx_gm_retained *idx = NULL;
+  int rc;
+  if (!pack_list(env, argv[0], &tb, &to, &n)) return enif_make_badarg(env);
+  if (argc > 1) {
+    unsigned len;
+    unsigned long v;
+    ERL_NIF_TERM h, t = argv[1];
+    if (!enif_get_list_length(env, t, &len) || len != n) goto badarg;
+    ex = enif_alloc(sizeof(uint64_t) * (n ? n : 1));
+    while (enif_get_list_cell(env, t, &h, &t)) {
+      if (!enif_get_ulong(env, h, &v)) goto badarg;
+      ex[i++] = v;
+    }
+  }
+  rc = emqx_gm_retained_build(CTX, tb, to, n, NULL, ex, 0, &idx);
+  enif_free(tb);
+  enif_free(to);
+  if (ex) enif_free(ex);
+  if (rc != EMQX_GM_OK) return error_tuple(env, rc);
+  return make_retained_term(env, idx);
+badarg:
+  enif_free(tb);
+  enif_free(to);
+  if (ex) enif_free(ex);
+  return enif_make_badarg(env);
+}
+
+/* match_retained(Index, [Filter], NowMs) -> [[Id]]
+ * emqx_retainer_mnesia:match_messages/1 per filter (:210-214), each row in
+ * topic order; the caller reads its messages by id and sorts them by timestamp
+ * (sort_retained/1) */
+static ERL_NIF_TERM match_retained(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_retained_res *r;
+  uint8_t *fb;
+  uint64_t *fo, n, i, k;
+  unsigned long now;
+  emqx_gm_csr out;
+  ERL_NIF_TERM result, *rows;
+  int rc;
+  (void)argc;
+  if (!enif_get_resource(env, argv[0], RETAINED_RT, (void **)&r) || !enif_get_ulong(env, argv[2], &now))
+    return enif_make_badarg(env);
+  if (!pack_list(env, argv[1], &fb, &fo, &n)) return enif_make_badarg(env);
+  rc = emqx_gm_retained_match(CTX, r->idx, fb, fo, n, now, 0, &out);
+  enif_free(fb);
+  enif_free(fo);
+  if (rc != EMQX_GM_OK) return error_tuple(env, rc);
+  rows = enif_alloc(sizeof(ERL_NIF_TERM) * (n ? n : 1));
+  for (i = 0; i < n; ++i) {
+    ERL_NIF_TERM row = enif_make_list(env, 0);
+    for (k = out.row_off[i + 1]; k > out.row_off[i]; --k)
+      row = enif_make_list_cell(env, enif_make_uint(env, out.ids[k - 1]), row);
+    rows[i] = row;
+  }
+  result = enif_make_list_from_array(env, rows, (unsigned)n);
+  enif_free(rows);
+  emqx_gm_csr_free(CTX, &out);
+  return result;
+}
+
+/* expire_retained(Index, [{Topic, ExpiryMs}]) -> {ok, NFound}
+ * delete_message/2 of a literal topic (ExpiryMs = 1, :117-128) or a refreshed
+ * message on a stored topic; mutates the table in place (emqx_gm_retained_expire) */
+static ERL_NIF_TERM expire_retained(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_retained_res *r;
+  unsigned len, i = 0;
+  ERL_NIF_TERM h, t, *topics, list;
+  uint8_t *tb;
+  uint64_t *to, n, *ex, found = 0;
+  int rc, ok = 1;
+  (void)argc;
+  if (!enif_get_resource(env, argv[0], RETAINED_RT, (void **)&r) || !enif_get_list_length(env, argv[1], &len))
+    return enif_make_badarg(env);
+  topics = enif_alloc(sizeof(ERL_NIF_TERM) * (len ? len : 1));
+  ex = enif_alloc(sizeof(uint64_t) * (len ? len : 1));
+  t = argv[1];
+  while (ok && enif_get_list_cell(env, t, &h, &t)) {
+    const ERL_NIF_TERM *tup;
+    int arity;
+    unsigned long v;
+    ok = enif_get_tuple(env, h, &arity, &tup) && arity == 2 && enif_get_ulong(env, tup[1], &v);
+    if (ok) {
+      topics[i] = tup[0];
+      ex[i++] = v;
+    }
+  }
+  list = enif_make_list_from_array(env, topics, i);
+  enif_free(topics);
+  if (!ok || !pack_list(env, list, &tb, &to, &n)) {
+    enif_free(ex);
+    return enif_make_badarg(env);
+  }
+  rc = emqx_gm_retained_expire(CTX, r->idx, tb, to, n, ex, &found);
+  enif_free(tb);
+  enif_free(to);
+  enif_free(ex);
+  if (rc != EMQX_GM_OK) return error_tuple(env, rc);
+  return enif_make_tuple2(env, A_OK, enif_make_uint(env, (unsigned)found));
+}
+
 static ErlNifFunc funcs[] = {
     {"load_index", 1, load_index, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"load_index", 2, load_index, ERL_NIF_DIRTY_JOB_CPU_BOUND},
@@ -498,6 +631,10 @@ static ErlNifFunc funcs[] = {
     {"empty", 1, empty, 0},
     {"export_index", 1, export_index, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"import_index", 1, import_index, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"load_retained", 1, load_retained, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"load_retained", 2, load_retained, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"match_retained", 3, match_retained, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"expire_retained", 2, expire_retained, ERL_NIF_DIRTY_JOB_CPU_BOUND},
 };
 
 ERL_NIF_INIT(emqx_gpu_match, funcs, load, NULL, NULL, unload)
