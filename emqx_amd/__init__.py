@@ -10,9 +10,10 @@ from .engine import Context, DeviceCsr, Index, gen_filter_codes, pack, render_co
 from .routing import Broker, Router, SessionRouter, Trie, default_context  # noqa: F401
 from .rules import TopicRuleIndex  # noqa: F401
 from .retainer import RetainedIndex, Retainer  # noqa: F401
+from .shared import SharedSub, SharedTable  # noqa: F401
 from . import topic  # noqa: F401
 
 __all__ = ["Context", "Index", "DeviceCsr", "Trie", "Router", "SessionRouter", "Broker", "TopicRuleIndex", "topic",
-           "RetainedIndex", "Retainer",
+           "RetainedIndex", "Retainer", "SharedTable", "SharedSub",
            "GpuMatchError",
            "pack", "gen_filter_codes", "render_codes", "default_context"]

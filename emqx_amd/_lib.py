@@ -18,6 +18,7 @@ WITH_EXACT = 0x1
 DEVICE_IO = 0x2
 NO_TIMING = 0x4
 RET_TIMED = 0x1
+SHARE_HASH, SHARE_ROUND_ROBIN, SHARE_STICKY, SHARE_RANDOM = 0, 1, 2, 3
 OPEN_MIRROR_EAGER = 0x1
 OPEN_MIRROR_LAZY = 0x2
 IMAGE_NO_BLOB = 0x1
@@ -69,6 +70,11 @@ class RetainedInfo(C.Structure):
     _fields_ = [("n_topics", C.c_uint64), ("n_nodes", C.c_uint64), ("n_words", C.c_uint64),
                 ("device_bytes", C.c_uint64), ("widest_level", C.c_uint64), ("walk_ws_bytes", C.c_uint64),
                 ("depth_max", C.c_uint32), ("lds_frames", C.c_int32)]
+
+
+class SharedInfo(C.Structure):
+    _fields_ = [("n_slots", C.c_uint64), ("n_members", C.c_uint64), ("n_filters_with_slots", C.c_uint64),
+                ("device_bytes", C.c_uint64)]
 
 
 UPD_KINDS = {0: "none", 1: "patch", 2: "overlay", 3: "rebuild", 4: "subs_only", 5: "build", 6: "import", 7: "shift"}
@@ -124,6 +130,11 @@ SIGNATURES = {
     "emqx_gm_retained_expire": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
     "emqx_gm_retained_info": (_i32, [_vp, C.POINTER(RetainedInfo)]),
     "emqx_gm_retained_release": (_i32, [_vp]),
+    "emqx_gm_shared_build": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, C.POINTER(_vp)]),
+    "emqx_gm_shared_pick": (_i32, [_vp, _vp, C.POINTER(Csr), _u32, _vp, _u32, C.POINTER(Csr), C.POINTER(Csr)]),
+    "emqx_gm_shared_slot": (_i32, [_vp, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_vp), C.POINTER(_u64)]),
+    "emqx_gm_shared_info": (_i32, [_vp, C.POINTER(SharedInfo)]),
+    "emqx_gm_shared_release": (_i32, [_vp]),
     # emqx_gm_ext.h
     "emqx_gm_gen_filter_codes": (_i32, [_u64, _u64, _i32, _vp]),
     "emqx_gm_render_codes": (_u64, [_vp, _u64, _vp, _vp]),
@@ -145,6 +156,12 @@ SIGNATURES = {
     "emqx_gm_retained_match_host": (_i32, [_vp, _vp, _vp, _u64, _u64, C.POINTER(Csr)]),
     "emqx_gm_retained_csr_free_host": (_i32, [C.POINTER(Csr)]),
     "emqx_gm_retained_last_times": (_i32, [_vp, C.POINTER(C.c_double)]),
+    "emqx_gm_shared_compile_host": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "emqx_gm_shared_pick_host": (_i32, [_vp, C.POINTER(Csr), _u32, _vp, _u32, C.POINTER(Csr), C.POINTER(Csr)]),
+    "emqx_gm_shared_csr_free_host": (_i32, [C.POINTER(Csr)]),
+    "emqx_gm_shared_pick_chunked": (_i32, [_vp, _vp, C.POINTER(Csr), _u32, _vp, _u32, _u32, C.POINTER(Csr),
+                                           C.POINTER(Csr)]),
+    "emqx_gm_shared_last_times": (_i32, [_vp, C.POINTER(C.c_double)]),
 }
 
 _LIB = None

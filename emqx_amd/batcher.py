@@ -34,6 +34,7 @@ from __future__ import annotations
 
 import threading
 import time
+import zlib
 from concurrent.futures import Future
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
@@ -148,6 +149,11 @@ class GpuRoutes:
 
     # ---- the batch call (fanout_batch/2)
     def groups(self, topics: Sequence[bytes]) -> List[Row]:
+        return self.groups_rows(topics)[0]
+
+    def groups_rows(self, topics: Sequence[bytes]):
+        """``groups`` plus what it was cut from: (rows, snapshot, (row_off, filter
+        ids)) -- the matched rows a SharedSub.dispatch_batch picks from."""
         self.refresh()
         if self.stale:
             raise RuntimeError("stale_index")
@@ -166,7 +172,7 @@ class GpuRoutes:
                 pos += c
             assert pos == int(fro[k + 1])
             out.append(row)
-        return out
+        return out, idx, (ro, ids)
 
 
 class PublishBatcher:
@@ -188,7 +194,17 @@ class PublishBatcher:
     (the ?OTHER table the Erlang caller reads directly) and ``subscribers`` to
     ``routes.subs``.  A ``groups_fn`` that is a bound ``GpuRoutes.groups`` gets
     its ``others`` the same way, so remote and shared routes cannot be dropped
-    by forgetting the second argument."""
+    by forgetting the second argument.
+
+    ``shared`` (a SharedSub; needs ``routes``): a window's shared deliveries are
+    resolved with ONE ``shared.dispatch_batch`` over the window's matched rows
+    (strategy ``shared_strategy``; ``shared_hash(topic, msg) -> u32`` stands in
+    for erlang:phash2/1 of the client id or source topic, default: CRC-32 of
+    the topic) instead of one ``shared_dispatch`` call per message and group.
+    The picked member gets ``deliver(sub, filter, msg)``; if that fails the
+    caller walks the rest of subscribers/2, as dispatch/4's FailedSubs loop
+    does.  A group the table holds no member for goes to ``shared_dispatch``.
+    Without ``shared`` nothing changes."""
 
     def __init__(self, groups_fn: Optional[Callable[[Sequence[bytes]], List[Row]]] = None, max_batch: int = 4096,
                  window_s: float = 0.001, subscribers: Optional[Dict[int, object]] = None,
@@ -201,7 +217,8 @@ class PublishBatcher:
                  fallback_dispatch: Optional[Callable[[bytes, object], object]] = None,
                  on_dropped: Optional[Callable[[object], None]] = None,
                  persist: Optional[Callable[[bytes, object], None]] = None,
-                 routes: Optional[GpuRoutes] = None):
+                 routes: Optional[GpuRoutes] = None, shared=None, shared_strategy: str = "round_robin",
+                 shared_hash: Optional[Callable[[bytes, object], int]] = None):
         if routes is None and isinstance(getattr(groups_fn, "__self__", None), GpuRoutes):
             routes = groups_fn.__self__
         if groups_fn is None:
@@ -213,6 +230,10 @@ class PublishBatcher:
                 others = routes.other
             if subscribers is None:
                 subscribers = routes.subs
+        if shared is not None and routes is None:
+            raise TypeError("PublishBatcher(shared=...) needs routes (the window's matched rows)")
+        self.routes, self.shared, self.shared_strategy = routes, shared, shared_strategy
+        self.shared_hash = shared_hash or (lambda topic, msg: zlib.crc32(topic))
         self.groups_fn = groups_fn
         self.max_batch = max_batch
         self.window_s = window_s
@@ -300,8 +321,16 @@ class PublishBatcher:
                     self._cv.wait(timeout=wait)
             self.poll()
 
-    def _rows(self, topics: Sequence[bytes]):
+    def _rows(self, topics: Sequence[bytes], msgs: Optional[Sequence[object]] = None):
         try:
+            if self.shared is not None:  # the window's shared picks: one device call
+                rows, idx, csr = self.routes.groups_rows(list(topics))
+                hashes = None
+                if self.shared_strategy.startswith("hash"):
+                    msgs = msgs if msgs is not None else [None] * len(topics)
+                    hashes = [self.shared_hash(t, m) & 0xFFFFFFFF for t, m in zip(topics, msgs)]
+                picks = self.shared.dispatch_batch(idx, csr, self.shared_strategy, hashes)
+                return [("ok", r, p) for r, p in zip(rows, picks)]
             return [("ok", r) for r in self.groups_fn(list(topics))]
         except Exception as e:  # the NIF's {error, _}: every caller takes the reference path
             return [("error", str(e))] * len(topics)
@@ -337,7 +366,7 @@ class PublishBatcher:
     def publish_batch(self, items: Sequence[Tuple[object, object]]) -> List[Result]:
         """Messages the caller already holds: one groups call, results in order."""
         topics = [self.prepare(t, m) for t, m in items]
-        rows = self._rows(topics)
+        rows = self._rows(topics, [m for _, m in items])
         with self._mlock:
             self.batches += 1
             self.messages += len(topics)
@@ -351,13 +380,14 @@ class PublishBatcher:
                      if isinstance(d, tuple) or _b(d) != self.node]
         else:  # the reference path
             routes, other = [], list(self.fallback(topic)) if self.fallback else []
+        picks = {(_b(g), f): sub for g, f, sub in row[2]} if len(row) > 2 else None
         routes += self.aggre(other)
         if not routes:  # route([], _): no subscribers anywhere
             self.dropped(topic, msg)
             return []
         out: Result = []
         for r in routes:  # lists:foldl prepending, as route/2
-            out.insert(0, self.do_route(r, topic, msg))
+            out.insert(0, self.do_route(r, topic, msg, picks))
         return out
 
     @staticmethod
@@ -367,16 +397,28 @@ class PublishBatcher:
         groups = sorted({(f, ("group", d[0])) for f, d in routes if isinstance(d, tuple)})
         return nodes + groups
 
-    def do_route(self, r, topic: bytes, msg):
+    def do_route(self, r, topic: bytes, msg, picks=None):
         if len(r) == 3:  # a local route with the GPU fan-out's subscriber ids
             f, node, ids = r
             return (node, f, self.dispatch_ids(f, ids, topic, msg))
         f, d = r
         if isinstance(d, tuple):  # ("group", G): emqx_shared_sub:dispatch/3
+            if picks is not None and (_b(d[1]), f) in picks:
+                return ("share", f, self.deliver_shared(d[1], f, picks[(_b(d[1]), f)], msg))
             return ("share", f, self.shared_dispatch(d[1], f, msg))
         if _b(d) == self.node:
             return (d, f, self.fallback_dispatch(f, msg))
         return (d, f, self.forward(d, f, msg))
+
+    def deliver_shared(self, group, f: bytes, sub, msg):
+        """dispatch/4 (emqx_shared_sub.erl:118-130) from the window's pick on: the
+        picked member first, then the others of subscribers/2 (FailedSubs)."""
+        if self.deliver(sub, f, msg):
+            return ("ok", 1)
+        for other in self.shared.subscribers(group, f):
+            if other is not sub and self.deliver(other, f, msg):
+                return ("ok", 1)
+        return ("error", "no_subscribers")
 
     def dispatch_ids(self, f: bytes, ids, topic: bytes, msg):
         """do_dispatch/2,3: one delivery per live subscriber; none live is a drop."""

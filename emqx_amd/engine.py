@@ -375,6 +375,13 @@ class Context:
         from .retainer import build_retained
         return build_retained(self, topics, ids, expiry_ms)
 
+    def build_shared(self, index: Index, slots, prev=None):
+        """A shared-subscription table bound to ``index`` (emqx_gm_shared_build):
+        ``slots`` is [(filter, group id, [member ids])]; ``prev`` hands on the
+        round-robin / sticky state, see :mod:`emqx_amd.shared`."""
+        from .shared import build_shared
+        return build_shared(self, index, slots, prev)
+
     # ------------------------------------------------------------------ match
     def match(self, index: Index, topics, exact: bool = True) -> Tuple[np.ndarray, np.ndarray]:
         """Batch emqx_router:match_routes/1 (exact=True) or emqx_trie:match/1

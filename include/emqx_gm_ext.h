@@ -138,6 +138,31 @@ int emqx_gm_retained_match_host(const emqx_gm_retained *idx, const uint8_t *filt
 int emqx_gm_retained_csr_free_host(emqx_gm_csr *csr);
 int emqx_gm_retained_last_times(const emqx_gm_retained *idx, double *ms3);
 
+/* Test and measurement support for the shared-subscription table (no product
+ * path uses these).  compile_host: the table compiled on the host alone against
+ * the filter set index_filter_* as emqx_gm_index_compile_host compiles it (ids
+ * = ranks among the distinct filters; no device, no context); prev must be a
+ * host-only table too; emqx_gm_shared_pick refuses the result.  pick_host: the
+ * single-threaded walk of emqx_gm_shared_pick over the same tables and the
+ * host-only table's own state (host rows; refused on a device table, whose
+ * state lives on the device); the CSRs are malloc'd (free with
+ * emqx_gm_shared_csr_free_host).  pick_chunked: emqx_gm_shared_pick with the
+ * round-robin chunk count forced (0: the library's rule, at most 1024).
+ * last_times: device ms of the last pick's enumerate, expand and round-robin
+ * passes, and of the whole call on the stream. */
+int emqx_gm_shared_compile_host(const uint8_t *index_filter_bytes, const uint64_t *index_filter_off,
+                                uint64_t n_index_filters, const uint8_t *filter_bytes, const uint64_t *filter_off,
+                                const uint32_t *group_ids, uint64_t n_slots, const uint64_t *mem_off,
+                                const uint32_t *mem_ids, const emqx_gm_shared *prev, emqx_gm_shared **out);
+int emqx_gm_shared_pick_host(emqx_gm_shared *sh, const emqx_gm_csr *matches, uint32_t strategy,
+                             const uint32_t *msg_hash, uint32_t seed, emqx_gm_csr *out_members,
+                             emqx_gm_csr *out_slots);
+int emqx_gm_shared_csr_free_host(emqx_gm_csr *csr);
+int emqx_gm_shared_pick_chunked(emqx_gm_ctx *ctx, emqx_gm_shared *sh, const emqx_gm_csr *matches,
+                                uint32_t strategy, const uint32_t *msg_hash, uint32_t seed, uint32_t n_chunks,
+                                emqx_gm_csr *out_members, emqx_gm_csr *out_slots);
+int emqx_gm_shared_last_times(const emqx_gm_shared *sh, double *ms4);
+
 #ifdef __cplusplus
 }
 #endif

@@ -516,6 +516,99 @@ int emqx_gm_retained_info(const emqx_gm_retained *idx, emqx_gm_retained_info_t *
 /* emqx_retainer_mnesia:clean/1 of this table (:160-162) */
 int emqx_gm_retained_release(emqx_gm_retained *idx);
 
+/* ---- shared-subscription dispatch (gm_shared.cpp / gm_shared.hip): one group member per match ----
+ * A filter routed to a shared group ('$share/Group/Filter', dest {Group, Node})
+ * comes back from a match as a route mark only; the reference then calls
+ * emqx_shared_sub:dispatch/3 once per message and group, which picks ONE member
+ * of the group (pick/6, do_pick/6, pick_subscriber/6, do_pick_subscriber/6,
+ * apps/emqx/src/emqx_shared_sub.erl:113-130, 234-288).  Here the picks of a
+ * whole publish window are computed in one device call, bit-equal to running
+ * pick/6 hit by hit in batch order in one publisher process.
+ * A SLOT is one {Group, Filter} pair with its member list (subscribers/2,
+ * :287-288: an ets bag -- insertion order, an identical member stored once).
+ * A HIT is a (message row, matched filter id, slot of that filter) triple;
+ * BATCH ORDER is rows ascending, filter ids in the order the row holds them,
+ * then the filter's slots ascending by group id.  For a hit on slot s with
+ * Count members (state per slot, kept in the table; mix / mix3 as defined in
+ * gm_shared.h: fmix(h) is the 32-bit finalizer h ^= h >> 16, h *= 0x85EBCA6B,
+ * h ^= h >> 13, h *= 0xC2B2AE35, h ^= h >> 16; mix(a, b) = fmix(fmix(a +
+ * 0x9E3779B9) + b); mix3(a, r, s) = mix(mix(a, r), s); all mod 2^32):
+ *   EMQX_GM_SHARE_HASH (hash_clientid, hash_topic, hash; :272-278):
+ *     members[msg_hash[row] rem Count]; the caller computes erlang:phash2/1 of
+ *     the client id or the source topic per message.
+ *   EMQX_GM_SHARE_ROUND_ROBIN (:279-285): Rem = rr[s] unset ? mix(seed, s) rem
+ *     Count : (rr[s] + 1) rem Count with the CURRENT Count; rr[s] = Rem; pick
+ *     members[Rem].  The reference draws the unset start with rand:uniform/1.
+ *   EMQX_GM_SHARE_STICKY (:234-247): st[s] while set, else members[mix(seed, s)
+ *     rem Count], which is stored (also for Count = 1, as :245 does).
+ *     Deviation: the reference keeps a sticky pid while its PROCESS is alive,
+ *     even after it unsubscribed (:236, is_active_sub); the table knows
+ *     membership, not liveness, so a member that left the list loses
+ *     stickiness at the next build.
+ *   EMQX_GM_SHARE_RANDOM (:270-271): members[mix3(seed, row, s) rem Count]:
+ *     counter based and stateless, equal arguments give equal picks (any
+ *     in-range choice is a valid outcome of rand:uniform/1).
+ *   Count = 1 picks that member; hash, round_robin and random read and write
+ *   no state then (pick_subscriber/6, first clause, :265).
+ * FailedSubs, the ack / nack retry loop of dispatch/4 (:118-130) and {error,
+ * no_subscribers} stay with the caller, which reads a slot's member list with
+ * emqx_gm_shared_slot.  A slot without members does not exist (the reference
+ * deletes the route). */
+typedef struct emqx_gm_shared emqx_gm_shared;
+#define EMQX_GM_SHARE_HASH 0u
+#define EMQX_GM_SHARE_ROUND_ROBIN 1u
+#define EMQX_GM_SHARE_STICKY 2u
+#define EMQX_GM_SHARE_RANDOM 3u
+typedef struct {
+  uint64_t n_slots;              /* {Group, Filter} pairs with members               */
+  uint64_t n_members;            /* member entries over all slots                    */
+  uint64_t n_filters_with_slots; /* distinct filters that carry a slot               */
+  uint64_t device_bytes;         /* resident table bytes in HBM (0: host-only table) */
+} emqx_gm_shared_info_t;
+/* The emqx_shared_subscription table (emqx_shared_sub.erl:287-288) bound to ONE
+ * plain snapshot `idx`, which it retains.  Input slot i is filter
+ * filter_bytes[filter_off[i] .. filter_off[i+1]) -- it must be a filter of the
+ * snapshot, else EMQX_GM_EINVAL with the filter named in emqx_gm_last_error --
+ * with the caller's group id group_ids[i] and members mem_ids[mem_off[i] ..
+ * mem_off[i+1]), ids in the same space as emqx_gm_index_build's subscriber ids
+ * (2^32 - 1 is reserved).  Slots are sorted by (filter id, group id); inputs
+ * with equal (filter, group) are merged in input order; a member listed twice
+ * is kept once, at its first place; empty slots are dropped.  prev (optional,
+ * not modified): rr / st are carried over for every slot whose (filter bytes,
+ * group id) exists in both -- filter ids shift between snapshots -- st only if
+ * that member is still listed.  flags: 0.  Sharded, shard and overlay
+ * snapshots: EMQX_GM_EUNSUPPORTED.  Offsets are checked as
+ * emqx_gm_retained_build checks them.  On a multi-device context the table
+ * lives on the first listed device. */
+int emqx_gm_shared_build(emqx_gm_ctx *ctx, emqx_gm_index *idx, const uint8_t *filter_bytes,
+                         const uint64_t *filter_off, const uint32_t *group_ids, uint64_t n_slots,
+                         const uint64_t *mem_off, const uint32_t *mem_ids, const emqx_gm_shared *prev,
+                         uint32_t flags, emqx_gm_shared **out);
+/* emqx_shared_sub:pick/6 (:234-288) for every hit of `matches`, rows of the
+ * bound snapshot as emqx_gm_match returns them: a host CSR, or a device CSR
+ * (on_device; msg_hash is then a device pointer too).  The results come back on
+ * the same side, with identical row_off and one entry per hit in batch order:
+ * out_members->ids the picked member, out_slots->ids the slot (free both with
+ * emqx_gm_csr_free).  msg_hash (n_rows entries) is required for
+ * EMQX_GM_SHARE_HASH and ignored otherwise.  Host rows are checked before any
+ * device work (n_rows < 2^32 - 1, row_off from 0 to nnz ascending, every id <
+ * n_filters: else EMQX_GM_EINVAL); for device rows the kernels skip an id >=
+ * n_filters and clamp an offset past nnz.  2^32 - 1 hits or more in one call:
+ * EMQX_GM_EOVERFLOW (no state changed).  Calls on one table are serialized
+ * and its state changes in stream order. */
+int emqx_gm_shared_pick(emqx_gm_ctx *ctx, emqx_gm_shared *sh, const emqx_gm_csr *matches, uint32_t strategy,
+                        const uint32_t *msg_hash, uint32_t seed, emqx_gm_csr *out_members,
+                        emqx_gm_csr *out_slots);
+/* subscribers(Group, Topic) of slot `slot` (:287-288; host memory owned by the
+ * table) for the caller's FailedSubs loop (dispatch/4, :118-130), and the
+ * slot's filter id in the bound snapshot and group id.  Any out pointer may be
+ * NULL. */
+int emqx_gm_shared_slot(const emqx_gm_shared *sh, uint32_t slot, uint32_t *filter_id, uint32_t *group_id,
+                        const uint32_t **members, uint64_t *n_members);
+int emqx_gm_shared_info(const emqx_gm_shared *sh, emqx_gm_shared_info_t *info);
+/* drops the table and its reference on the snapshot */
+int emqx_gm_shared_release(emqx_gm_shared *sh);
+
 #ifdef __cplusplus
 }
 #endif

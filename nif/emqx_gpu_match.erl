@@ -13,6 +13,7 @@
 -export([load_index/1, load_index/2, load_index_sharded/1, load_index_sharded/2, update_index/2, update_subs/2,
          match_batch/2, match_routes_batch/2, fanout_batch/2, empty/1, export_index/1, import_index/1]).
 -export([load_retained/1, load_retained/2, match_retained/3, expire_retained/2]).
+-export([load_shared/3, load_shared/4, pick_shared/4, pick_shared_nif/5]).
 -export([match/2]).
 
 -on_load(init/0).
@@ -111,6 +112,43 @@ match_retained(_Index, _Filters, _NowMs) -> erlang:nif_error(nif_not_loaded).
 %% how many of the topics were stored.
 -spec expire_retained(reference(), [{binary(), non_neg_integer()}]) -> {ok, non_neg_integer()} | {error, term()}.
 expire_retained(_Index, _TopicExpiries) -> erlang:nif_error(nif_not_loaded).
+
+%% The emqx_shared_subscription table (emqx_shared_sub.erl:287-288) bound to the
+%% snapshot Index: one member list per {Filter, GroupId}, members in
+%% subscription order; every Filter must be a filter of the snapshot (its shared
+%% route).  Prev hands on the round_robin / sticky state of the slots both
+%% tables hold (emqx_gm_shared_build).  On a node with several GPUs the table
+%% lives on the first one.
+-spec load_shared(reference(), [{binary(), non_neg_integer()}], [[non_neg_integer()]]) ->
+          {ok, reference()} | {error, term()}.
+load_shared(_Index, _Slots, _Members) -> erlang:nif_error(nif_not_loaded).
+
+-spec load_shared(reference(), [{binary(), non_neg_integer()}], [[non_neg_integer()]], reference()) ->
+          {ok, reference()} | {error, term()}.
+load_shared(_Index, _Slots, _Members, _Prev) -> erlang:nif_error(nif_not_loaded).
+
+%% emqx_shared_sub:dispatch/3's pick (pick/6, :234-288) for a whole publish
+%% window: per message {Topic, ClientId}, in order, [{Filter, {GroupId,
+%% MemberId}}] for every shared {Group, Filter} the topic matches.  The hash
+%% strategies hash here, as do_pick_subscriber/6 does (:272-278); random draws
+%% and unset round_robin / sticky starts derive from Seed.  FailedSubs and the
+%% ack / nack retry of dispatch/4 (:118-130) stay with the caller.
+-spec pick_shared(reference(), [{binary(), term()}], atom(), non_neg_integer()) ->
+          [[{binary(), {non_neg_integer(), non_neg_integer()}}]] | {error, term()}.
+pick_shared(Table, Msgs, Strategy, Seed) ->
+    Topics = [T || {T, _} <- Msgs],
+    {S, Hashes} = case Strategy of
+                      hash_topic -> {0, [erlang:phash2(T) || {T, _} <- Msgs]};
+                      H when H =:= hash; H =:= hash_clientid -> {0, [erlang:phash2(C) || {_, C} <- Msgs]};
+                      round_robin -> {1, []};
+                      sticky -> {2, []};
+                      random -> {3, []}
+                  end,
+    pick_shared_nif(Table, Topics, S, Hashes, Seed band 16#FFFFFFFF).
+
+-spec pick_shared_nif(reference(), [binary()], 0..3, [non_neg_integer()], non_neg_integer()) ->
+          [[{binary(), {non_neg_integer(), non_neg_integer()}}]] | {error, term()}.
+pick_shared_nif(_Table, _Topics, _Strategy, _Hashes, _Seed) -> erlang:nif_error(nif_not_loaded).
 
 %% emqx_trie:match/1 drop-in with fallback.
 -spec match(reference(), binary()) -> [binary()].

@@ -30,7 +30,12 @@ typedef struct {
   emqx_gm_retained *idx;
 } gm_retained_res;
 
-static ErlNifResourceType *INDEX_RT, *RETAINED_RT;
+typedef struct {
+  emqx_gm_shared *sh; /* retains its snapshot: filter binaries made over this resource stay valid */
+  emqx_gm_index *idx;
+} gm_shared_res;
+
+static ErlNifResourceType *INDEX_RT, *RETAINED_RT, *SHARED_RT;
 static emqx_gm_ctx *CTX;
 static ERL_NIF_TERM A_OK, A_ERROR, A_BADARG, A_INSERT, A_DELETE, A_SUBSCRIBE, A_UNSUBSCRIBE, A_ROUTE_ADD,
     A_ROUTE_DELETE;
@@ -45,6 +50,12 @@ static void retained_dtor(ErlNifEnv *env, void *obj) {
   gm_retained_res *r = (gm_retained_res *)obj;
   (void)env;
   if (r->idx) emqx_gm_retained_release(r->idx);
+}
+
+static void shared_dtor(ErlNifEnv *env, void *obj) {
+  gm_shared_res *r = (gm_shared_res *)obj;
+  (void)env;
+  if (r->sh) emqx_gm_shared_release(r->sh);
 }
 
 /* LoadInfo (erlang:load_nif/2): a device ordinal, or the node's device list
@@ -72,6 +83,7 @@ static int load(ErlNifEnv *env, void **priv, ERL_NIF_TERM info) {
   }
   INDEX_RT = enif_open_resource_type(env, NULL, "emqx_gm_index", index_dtor, ERL_NIF_RT_CREATE, NULL);
   RETAINED_RT = enif_open_resource_type(env, NULL, "emqx_gm_retained", retained_dtor, ERL_NIF_RT_CREATE, NULL);
+  SHARED_RT = enif_open_resource_type(env, NULL, "emqx_gm_shared", shared_dtor, ERL_NIF_RT_CREATE, NULL);
   A_OK = enif_make_atom(env, "ok");
   A_ERROR = enif_make_atom(env, "error");
   A_BADARG = enif_make_atom(env, "badarg");
@@ -81,7 +93,7 @@ static int load(ErlNifEnv *env, void **priv, ERL_NIF_TERM info) {
   A_UNSUBSCRIBE = enif_make_atom(env, "unsubscribe");
   A_ROUTE_ADD = enif_make_atom(env, "route_add");
   A_ROUTE_DELETE = enif_make_atom(env, "route_delete");
-  return emqx_gm_open(&o, &CTX) == EMQX_GM_OK && INDEX_RT && RETAINED_RT ? 0 : 1;
+  return emqx_gm_open(&o, &CTX) == EMQX_GM_OK && INDEX_RT && RETAINED_RT && SHARED_RT ? 0 : 1;
 }
 
 static void unload(ErlNifEnv *env, void *priv) {
@@ -618,6 +630,138 @@ static ERL_NIF_TERM expire_retained(ErlNifEnv *env, int argc, const ERL_NIF_TERM
   return enif_make_tuple2(env, A_OK, enif_make_uint(env, (unsigned)found));
 }
 
+/* ---- shared-subscription dispatch (emqx_gm_shared_*): emqx_shared_sub's member selection ----
+ * load_shared(Index, [{Filter, GroupId}], [[MemberId]]) | load_shared(.., Prev) -> {ok, Table}
+ * the emqx_shared_subscription table (emqx_shared_sub.erl:287-288) bound to the
+ * snapshot Index: one member list per {Filter, GroupId}, in subscription order;
+ * Prev hands on the round_robin / sticky state (emqx_gm_shared_build) */
+static ERL_NIF_TERM load_shared(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_index_res *ix;
+  gm_shared_res *prev = NULL, *res;
+  unsigned len, i = 0;
+  ERL_NIF_TERM h, t, *filters, list, term;
+  uint8_t *fb;
+  uint64_t *fo, n, *mo = NULL;
+  uint32_t *gids, *mi = NULL;
+  emqx_gm_shared *sh = NULL;
+  int rc, ok = 1;
+  if (!enif_get_resource(env, argv[0], INDEX_RT, (void **)&ix) || !enif_get_list_length(env, argv[1], &len))
+    return enif_make_badarg(env);
+  if (argc == 4 && !enif_get_resource(env, argv[3], SHARED_RT, (void **)&prev)) return enif_make_badarg(env);
+  filters = enif_alloc(sizeof(ERL_NIF_TERM) * (len ? len : 1));
+  gids = enif_alloc(sizeof(uint32_t) * (len ? len : 1));
+  t = argv[1];
+  while (ok && enif_get_list_cell(env, t, &h, &t)) {
+    const ERL_NIF_TERM *tup;
+    int arity;
+    unsigned g;
+    ok = enif_get_tuple(env, h, &arity, &tup) && arity == 2 && enif_get_uint(env, tup[1], &g);
+    if (ok) {
+      filters[i] = tup[0];
+      gids[i++] = g;
+    }
+  }
+  list = enif_make_list_from_array(env, filters, i);
+  enif_free(filters);
+  if (!ok || !pack_list(env, list, &fb, &fo, &n)) {
+    enif_free(gids);
+    return enif_make_badarg(env);
+  }
+  if (!pack_subs(env, argv[2], n, &mo, &mi)) {
+    enif_free(gids);
+    enif_free(fb);
+    enif_free(fo);
+    return enif_make_badarg(env);
+  }
+  rc = emqx_gm_shared_build(CTX, ix->idx, fb, fo, gids, n, mo, mi, prev ? prev->sh : NULL, 0, &sh);
+  enif_free(gids);
+  enif_free(fb);
+  enif_free(fo);
+  enif_free(mo);
+  enif_free(mi);
+  if (rc != EMQX_GM_OK) return error_tuple(env, rc);
+  res = enif_alloc_resource(SHARED_RT, sizeof(*res));
+  res->sh = sh;
+  res->idx = ix->idx; /* (kept alive by the table's own reference) */
+  term = enif_make_resource(env, res);
+  enif_release_resource(res);
+  return enif_make_tuple2(env, A_OK, term);
+}
+
+/* pick_shared_nif(Table, [Topic], Strategy :: 0..3, [Hash], Seed) -> [[{Filter, {GroupId, MemberId}}]]
+ * per topic, in batch order, the member emqx_shared_sub:pick/6 (:234-288) picks
+ * for every {Group, Filter} the topic matches: the match (match_routes/1) and
+ * the picks of the whole window, one emqx_gm_shared_pick.  Hashes (one per topic,
+ * erlang:phash2/1 of the client id or source topic, computed by the Erlang
+ * wrapper pick_shared/4) are read for Strategy 0 only. */
+static ERL_NIF_TERM pick_shared_nif(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_shared_res *r;
+  uint8_t *tb;
+  uint64_t *to, n, i, k;
+  unsigned strategy, seed, nh = 0, v;
+  uint32_t *hash = NULL;
+  emqx_gm_csr m, om, os;
+  ERL_NIF_TERM result, *rows, h, t;
+  int rc;
+  (void)argc;
+  if (!enif_get_resource(env, argv[0], SHARED_RT, (void **)&r) || !enif_get_uint(env, argv[2], &strategy) ||
+      !enif_get_list_length(env, argv[3], &nh) || !enif_get_uint(env, argv[4], &seed))
+    return enif_make_badarg(env);
+  if (!pack_topics(env, argv[1], &tb, &to, &n)) return enif_make_badarg(env);
+  if (strategy == EMQX_GM_SHARE_HASH) {
+    if (nh != n) {
+      free_topics(tb, to);
+      return enif_make_badarg(env);
+    }
+    hash = enif_alloc(sizeof(uint32_t) * (n ? n : 1));
+    t = argv[3];
+    i = 0;
+    while (enif_get_list_cell(env, t, &h, &t)) {
+      if (!enif_get_uint(env, h, &v)) {
+        enif_free(hash);
+        free_topics(tb, to);
+        return enif_make_badarg(env);
+      }
+      hash[i++] = v;
+    }
+  }
+  rc = emqx_gm_match(CTX, r->idx, tb, to, n, EMQX_GM_WITH_EXACT, &m);
+  free_topics(tb, to);
+  if (rc == EMQX_GM_OK) {
+    rc = emqx_gm_shared_pick(CTX, r->sh, &m, strategy, hash, seed, &om, &os);
+    emqx_gm_csr_free(CTX, &m);
+  }
+  if (hash) enif_free(hash);
+  if (rc != EMQX_GM_OK) return error_tuple(env, rc);
+  rows = enif_alloc(sizeof(ERL_NIF_TERM) * (n ? n : 1));
+  for (i = 0; i < n; ++i) {
+    ERL_NIF_TERM row = enif_make_list(env, 0);
+    for (k = om.row_off[i + 1]; k > om.row_off[i]; --k) {
+      const uint8_t *p = NULL;
+      uint64_t l = 0;
+      uint32_t f = 0, g = 0;
+      if (emqx_gm_shared_slot(r->sh, os.ids[k - 1], &f, &g, NULL, NULL) != EMQX_GM_OK ||
+          emqx_gm_index_filter(r->idx, f, &p, &l) != EMQX_GM_OK) {
+        enif_free(rows);
+        emqx_gm_csr_free(CTX, &om);
+        emqx_gm_csr_free(CTX, &os);
+        return error_tuple(env, EMQX_GM_EINVAL);
+      }
+      row = enif_make_list_cell(
+          env,
+          enif_make_tuple2(env, enif_make_resource_binary(env, r, p, l),
+                           enif_make_tuple2(env, enif_make_uint(env, g), enif_make_uint(env, om.ids[k - 1]))),
+          row);
+    }
+    rows[i] = row;
+  }
+  result = enif_make_list_from_array(env, rows, (unsigned)n);
+  enif_free(rows);
+  emqx_gm_csr_free(CTX, &om);
+  emqx_gm_csr_free(CTX, &os);
+  return result;
+}
+
 static ErlNifFunc funcs[] = {
     {"load_index", 1, load_index, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"load_index", 2, load_index, ERL_NIF_DIRTY_JOB_CPU_BOUND},
@@ -635,6 +779,9 @@ static ErlNifFunc funcs[] = {
     {"load_retained", 2, load_retained, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"match_retained", 3, match_retained, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"expire_retained", 2, expire_retained, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"load_shared", 3, load_shared, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"load_shared", 4, load_shared, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"pick_shared_nif", 5, pick_shared_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
 };
 
 ERL_NIF_INIT(emqx_gpu_match, funcs, load, NULL, NULL, unload)
