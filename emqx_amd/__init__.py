@@ -11,9 +11,10 @@ from .routing import Broker, Router, SessionRouter, Trie, default_context  # noq
 from .rules import TopicRuleIndex  # noqa: F401
 from .retainer import RetainedIndex, Retainer  # noqa: F401
 from .shared import SharedSub, SharedTable  # noqa: F401
+from .authz import Authz, AuthzTable  # noqa: F401
 from . import topic  # noqa: F401
 
 __all__ = ["Context", "Index", "DeviceCsr", "Trie", "Router", "SessionRouter", "Broker", "TopicRuleIndex", "topic",
-           "RetainedIndex", "Retainer", "SharedTable", "SharedSub",
+           "RetainedIndex", "Retainer", "SharedTable", "SharedSub", "Authz", "AuthzTable",
            "GpuMatchError",
            "pack", "gen_filter_codes", "render_codes", "default_context"]

@@ -18,6 +18,7 @@ WITH_EXACT = 0x1
 DEVICE_IO = 0x2
 NO_TIMING = 0x4
 RET_TIMED = 0x1
+AUTHZ_TIMED = 0x1
 SHARE_HASH, SHARE_ROUND_ROBIN, SHARE_STICKY, SHARE_RANDOM = 0, 1, 2, 3
 OPEN_MIRROR_EAGER = 0x1
 OPEN_MIRROR_LAZY = 0x2
@@ -75,6 +76,31 @@ class RetainedInfo(C.Structure):
 class SharedInfo(C.Structure):
     _fields_ = [("n_slots", C.c_uint64), ("n_members", C.c_uint64), ("n_filters_with_slots", C.c_uint64),
                 ("device_bytes", C.c_uint64)]
+
+
+class AuthzDesc(C.Structure):
+    _fields_ = [("n_segments", C.c_uint32), ("seg_kind", C.c_void_p), ("seg_range_off", C.c_void_p),
+                ("n_ranges", C.c_uint64), ("range_rule_off", C.c_void_p), ("key_bytes", C.c_void_p),
+                ("key_off", C.c_void_p), ("n_rules", C.c_uint64), ("rule_id", C.c_void_p),
+                ("rule_perm", C.c_void_p), ("rule_action", C.c_void_p), ("rule_who_op", C.c_void_p),
+                ("rule_who_off", C.c_void_p), ("rule_filter_off", C.c_void_p), ("n_leaves", C.c_uint64),
+                ("leaf_kind", C.c_void_p), ("leaf_bytes", C.c_void_p), ("leaf_off", C.c_void_p),
+                ("n_filters", C.c_uint64), ("filter_kind", C.c_void_p), ("filter_bytes", C.c_void_p),
+                ("filter_off", C.c_void_p)]
+
+
+class AuthzBatch(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("topic_bytes", C.c_void_p), ("topic_off", C.c_void_p),
+                ("clientid_bytes", C.c_void_p), ("clientid_off", C.c_void_p), ("username_bytes", C.c_void_p),
+                ("username_off", C.c_void_p), ("flags", C.c_void_p), ("peerhost", C.c_void_p),
+                ("action", C.c_void_p), ("re_mask", C.c_void_p)]
+
+
+class AuthzInfo(C.Structure):
+    _fields_ = [("build_ms", C.c_double), ("device_bytes", C.c_uint64), ("n_rules", C.c_uint64),
+                ("n_keys", C.c_uint64), ("n_words", C.c_uint64), ("n_filters", C.c_uint64),
+                ("n_leaves", C.c_uint64), ("n_segments", C.c_uint32), ("deepest_filter", C.c_uint32),
+                ("longest_range", C.c_uint64)]
 
 
 UPD_KINDS = {0: "none", 1: "patch", 2: "overlay", 3: "rebuild", 4: "subs_only", 5: "build", 6: "import", 7: "shift"}
@@ -135,6 +161,10 @@ SIGNATURES = {
     "emqx_gm_shared_slot": (_i32, [_vp, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_vp), C.POINTER(_u64)]),
     "emqx_gm_shared_info": (_i32, [_vp, C.POINTER(SharedInfo)]),
     "emqx_gm_shared_release": (_i32, [_vp]),
+    "emqx_gm_authz_build": (_i32, [_vp, C.POINTER(AuthzDesc), _u32, C.POINTER(_vp)]),
+    "emqx_gm_authz_check": (_i32, [_vp, _vp, C.POINTER(AuthzBatch), _u32, _vp, _vp]),
+    "emqx_gm_authz_info": (_i32, [_vp, C.POINTER(AuthzInfo)]),
+    "emqx_gm_authz_release": (_i32, [_vp]),
     # emqx_gm_ext.h
     "emqx_gm_gen_filter_codes": (_i32, [_u64, _u64, _i32, _vp]),
     "emqx_gm_render_codes": (_u64, [_vp, _u64, _vp, _vp]),
@@ -162,6 +192,9 @@ SIGNATURES = {
     "emqx_gm_shared_pick_chunked": (_i32, [_vp, _vp, C.POINTER(Csr), _u32, _vp, _u32, _u32, C.POINTER(Csr),
                                            C.POINTER(Csr)]),
     "emqx_gm_shared_last_times": (_i32, [_vp, C.POINTER(C.c_double)]),
+    "emqx_gm_authz_compile_host": (_i32, [C.POINTER(AuthzDesc), C.POINTER(_vp)]),
+    "emqx_gm_authz_check_host": (_i32, [_vp, C.POINTER(AuthzBatch), _vp, _vp]),
+    "emqx_gm_authz_last_kernel_ms": (_i32, [_vp, C.POINTER(C.c_double)]),
 }
 
 _LIB = None

@@ -382,6 +382,13 @@ class Context:
         from .shared import build_shared
         return build_shared(self, index, slots, prev)
 
+    def build_authz(self, table):
+        """An authorization table (emqx_gm_authz_build) from an ``AuthzTable``:
+        the chain of file and built-in-database sources compiled into HBM, see
+        :mod:`emqx_amd.authz`."""
+        from .authz import build_authz
+        return build_authz(self, table)
+
     # ------------------------------------------------------------------ match
     def match(self, index: Index, topics, exact: bool = True) -> Tuple[np.ndarray, np.ndarray]:
         """Batch emqx_router:match_routes/1 (exact=True) or emqx_trie:match/1

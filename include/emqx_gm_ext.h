@@ -163,6 +163,17 @@ int emqx_gm_shared_pick_chunked(emqx_gm_ctx *ctx, emqx_gm_shared *sh, const emqx
                                 emqx_gm_csr *out_members, emqx_gm_csr *out_slots);
 int emqx_gm_shared_last_times(const emqx_gm_shared *sh, double *ms4);
 
+/* Test and measurement support for the authorization table (no product path
+ * uses these).  compile_host: the table compiled on the host alone (no device,
+ * no context); emqx_gm_authz_check refuses it.  check_host: the walk of
+ * emqx_gm_authz_check over the host copy of the tables, single threaded, no
+ * device call.  last_kernel_ms: device ms of k_authz_check in the table's last
+ * EMQX_GM_AUTHZ_TIMED check (summed over a large window's chunks). */
+int emqx_gm_authz_compile_host(const emqx_gm_authz_desc *desc, emqx_gm_authz **out);
+int emqx_gm_authz_check_host(const emqx_gm_authz *tab, const emqx_gm_authz_batch *batch, uint8_t *verdict,
+                             uint32_t *rule);
+int emqx_gm_authz_last_kernel_ms(const emqx_gm_authz *tab, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -609,6 +609,153 @@ int emqx_gm_shared_info(const emqx_gm_shared *sh, emqx_gm_shared_info_t *info);
 /* drops the table and its reference on the snapshot */
 int emqx_gm_shared_release(emqx_gm_shared *sh);
 
+/* ---- authorization check (gm_authz.cpp / gm_authz.hip): the first matching ACL rule per request ----
+ * Every PUBLISH and SUBSCRIBE passes emqx_authz:authorize/5 before the router;
+ * the reference scans its rule lists per packet (emqx_authz:do_authorize/4,
+ * apps/emqx_authz/src/emqx_authz.erl:307-317; the file source,
+ * emqx_authz_rule:matches/4, emqx_authz_rule.erl:110-125; the built-in database,
+ * emqx_authz_mnesia:authorize/4, emqx_authz_mnesia.erl:95-111, 212-218).  Here
+ * the chain of file and built-in-database sources is compiled once into one table
+ * in HBM and a window of requests (clientinfo, action, topic) is answered in
+ * one device call, bit-equal to do_authorize/4 over that chain.
+ * The table is an ordered list of SEGMENTS; a request's evaluation order is the
+ * concatenation, in segment order, of the one rule range each segment yields
+ * for that client: a GLOBAL segment's one range for every client (a file
+ * source; the built-in database's `all` record), a BY_CLIENTID / BY_USERNAME
+ * segment's range under the request's own clientid / username (the keyed
+ * records; an undefined or absent key yields no rule).  [file,
+ * built_in_database] is GLOBAL, BY_CLIENTID, BY_USERNAME, GLOBAL.
+ * A RULE is {permission, who, action, topic filters} (emqx_authz_rule.erl:49)
+ * and the caller's u32 id.  match/4 (:119-125) = match_action/2 (:127-130) and
+ * match_who/2 (:132-165) and match_topics/3 (:167-180):
+ *   who: AND or OR over leaves (all = AND of none; the foldl identities make
+ *     AND [] true and OR [] false).  Leaves: username / clientid equal to given
+ *     bytes (an undefined username or clientid matches none); ipaddr / ipaddrs:
+ *     CIDRs as esockd_cidr:parse/2 compiles them, a family and an inclusive
+ *     [lo, hi] -- the families equal and lo <= peerhost <= hi, an undefined
+ *     peerhost matches none; regex k (k < 32): bit k of the request's re_mask --
+ *     the library runs no regex, the caller evaluates the table's at most 32
+ *     distinct {re, _} predicates once per client.  A nested and / or and a 33rd
+ *     regex are refused (EMQX_GM_EUNSUPPORTED).
+ *   topic filters (compile_topic/1, :82-91): any filter matching is enough, a
+ *     rule without filters never matches.  Words are split on '/', empty words
+ *     kept.  A plain filter is matched by the LIST clauses of emqx_topic:match/2
+ *     (apps/emqx/src/emqx_topic.erl:74-87) in their order -- NO '$'-rule, so '#'
+ *     authorizes '$SYS/x'; the request topic's words are opaque ('a/#' as a
+ *     SUBSCRIBE name matches the filter 'a/+', not 'a/b'; '#' before a filter's
+ *     last word equals only a name word '#').  EMQX_GM_AUTHZ_FILTER_EQ ({eq, T}
+ *     or "eq T"): equality of the word lists, placeholders not substituted.  A
+ *     plain filter holding '${clientid}' or '${username}' as a whole word is a
+ *     pattern (feed_var/3, :182-195): the word is replaced by the client's value
+ *     as ONE binary word -- a value "", "+", "#" or one holding '/' therefore
+ *     equals no name word -- and stays literal when the value is undefined.
+ * On a multi-device context the table lives on the first listed device.  A
+ * table is immutable: a changed ACL is a new build the caller swaps in. */
+typedef struct emqx_gm_authz emqx_gm_authz;
+#define EMQX_GM_AUTHZ_GLOBAL 0u
+#define EMQX_GM_AUTHZ_BY_CLIENTID 1u
+#define EMQX_GM_AUTHZ_BY_USERNAME 2u
+#define EMQX_GM_AUTHZ_ALLOW 1u /* rule_perm, and a verdict */
+#define EMQX_GM_AUTHZ_DENY 2u
+#define EMQX_GM_AUTHZ_NOMATCH 0u
+#define EMQX_GM_AUTHZ_PUBLISH 1u /* rule_action, and a request's action */
+#define EMQX_GM_AUTHZ_SUBSCRIBE 2u
+#define EMQX_GM_AUTHZ_ALL 3u /* rule_action only */
+#define EMQX_GM_AUTHZ_WHO_USERNAME 0u
+#define EMQX_GM_AUTHZ_WHO_CLIENTID 1u
+#define EMQX_GM_AUTHZ_WHO_IPADDR 2u /* ipaddr and ipaddrs: one or more CIDRs */
+#define EMQX_GM_AUTHZ_WHO_REGEX 3u
+#define EMQX_GM_AUTHZ_WHO_AND 4u /* a nested list: refused */
+#define EMQX_GM_AUTHZ_WHO_OR 5u
+#define EMQX_GM_AUTHZ_FILTER_PLAIN 0u /* a pattern if it holds a placeholder word */
+#define EMQX_GM_AUTHZ_FILTER_EQ 1u
+#define EMQX_GM_AUTHZ_CIDR_BYTES 33u /* family (4 | 6), lo[16], hi[16]; an IPv4 address in the first 4 of its 16 */
+#define EMQX_GM_AUTHZ_NO_RULE 0xFFFFFFFFu
+/* The table to compile.  Segment s owns ranges [seg_range_off[s], seg_range_off[s+1]):
+ * exactly one for a GLOBAL segment, one per key for a keyed one (a key listed
+ * twice in one segment: EMQX_GM_EINVAL).  Range k holds rules [range_rule_off[k],
+ * range_rule_off[k+1]) in evaluation order under the key key_bytes[key_off[k] ..
+ * key_off[k+1]) (ignored for a GLOBAL segment's).  Rule r: who leaves
+ * [rule_who_off[r], rule_who_off[r+1]) joined by rule_who_op[r] (0 AND, 1 OR),
+ * filters [rule_filter_off[r], rule_filter_off[r+1]).  Leaf l's argument is
+ * leaf_bytes[leaf_off[l] .. leaf_off[l+1]): the value's bytes (username,
+ * clientid), k * EMQX_GM_AUTHZ_CIDR_BYTES (ipaddr), or one byte k (regex). */
+typedef struct {
+  uint32_t n_segments;
+  const uint32_t *seg_kind;
+  const uint64_t *seg_range_off; /* [n_segments + 1] */
+  uint64_t n_ranges;
+  const uint64_t *range_rule_off; /* [n_ranges + 1] */
+  const uint8_t *key_bytes;
+  const uint64_t *key_off; /* [n_ranges + 1] */
+  uint64_t n_rules;
+  const uint32_t *rule_id;
+  const uint8_t *rule_perm;   /* EMQX_GM_AUTHZ_ALLOW / _DENY */
+  const uint8_t *rule_action; /* EMQX_GM_AUTHZ_PUBLISH / _SUBSCRIBE / _ALL */
+  const uint8_t *rule_who_op;
+  const uint64_t *rule_who_off;    /* [n_rules + 1] */
+  const uint64_t *rule_filter_off; /* [n_rules + 1] */
+  uint64_t n_leaves;
+  const uint8_t *leaf_kind; /* EMQX_GM_AUTHZ_WHO_* */
+  const uint8_t *leaf_bytes;
+  const uint64_t *leaf_off; /* [n_leaves + 1] */
+  uint64_t n_filters;
+  const uint8_t *filter_kind; /* EMQX_GM_AUTHZ_FILTER_* */
+  const uint8_t *filter_bytes;
+  const uint64_t *filter_off; /* [n_filters + 1] */
+} emqx_gm_authz_desc;
+/* A window of requests, host buffers.  flags[i]: which of the clientinfo's
+ * fields are defined (an undefined one's bytes are ignored). */
+#define EMQX_GM_AUTHZ_F_CLIENTID 0x1u
+#define EMQX_GM_AUTHZ_F_USERNAME 0x2u
+#define EMQX_GM_AUTHZ_F_PEERHOST 0x4u
+#define EMQX_GM_AUTHZ_F_IPV6 0x8u
+typedef struct {
+  uint64_t n;
+  const uint8_t *topic_bytes;
+  const uint64_t *topic_off; /* [n + 1] */
+  const uint8_t *clientid_bytes;
+  const uint64_t *clientid_off; /* [n + 1] */
+  const uint8_t *username_bytes;
+  const uint64_t *username_off; /* [n + 1] */
+  const uint8_t *flags;         /* [n] EMQX_GM_AUTHZ_F_* */
+  const uint8_t *peerhost;      /* [n][16] network order, an IPv4 address in the first 4 */
+  const uint8_t *action;        /* [n] EMQX_GM_AUTHZ_PUBLISH / _SUBSCRIBE */
+  const uint32_t *re_mask;      /* [n] bit k: the table's regex k matches this client */
+} emqx_gm_authz_batch;
+typedef struct {
+  double build_ms;         /* host compile (and upload) of this table           */
+  uint64_t device_bytes;   /* resident table bytes in HBM (0: host-only table)  */
+  uint64_t n_rules;
+  uint64_t n_keys;         /* keys over all keyed segments                      */
+  uint64_t n_words;        /* distinct filter words, the 5 reserved included    */
+  uint64_t n_filters;
+  uint64_t n_leaves;
+  uint32_t n_segments;
+  uint32_t deepest_filter; /* words of the deepest filter                       */
+  uint64_t longest_range;  /* rules of the longest range                        */
+} emqx_gm_authz_info_t;
+/* emqx_authz_rule:compile/1 (:55-94) of every rule and emqx_authz_mnesia:
+ * store_rules/2 (emqx_authz_mnesia.erl:123-132) of every record, into one device
+ * allocation.  Every offset array is checked as emqx_gm_retained_build checks
+ * its own (from 0, ascending, entries under 2 GiB, the last equal to the next
+ * array's count) and every code against its range (EMQX_GM_EINVAL) before any
+ * device work.  At most 64 segments.  flags: 0. */
+int emqx_gm_authz_build(emqx_gm_ctx *ctx, const emqx_gm_authz_desc *desc, uint32_t flags, emqx_gm_authz **out);
+/* emqx_authz:do_authorize/4 (emqx_authz.erl:307-317) for every request of the
+ * window: verdict[i] = EMQX_GM_AUTHZ_NOMATCH / _ALLOW / _DENY and rule[i] = the
+ * first matching rule's id (EMQX_GM_AUTHZ_NO_RULE on nomatch).  The default for
+ * nomatch (authorization.no_match, emqx_authz.erl:297-304) is the caller's.
+ * Host buffers; a window of up to 2^20 requests takes one device round trip.
+ * flags: 0 or EMQX_GM_AUTHZ_TIMED (the kernel is timed by device events). */
+#define EMQX_GM_AUTHZ_TIMED 0x1u
+int emqx_gm_authz_check(emqx_gm_ctx *ctx, const emqx_gm_authz *tab, const emqx_gm_authz_batch *batch,
+                        uint32_t flags, uint8_t *verdict, uint32_t *rule);
+/* emqx_authz_mnesia:record_count/0 (emqx_authz_mnesia.erl:175-177) and the table's shape */
+int emqx_gm_authz_info(const emqx_gm_authz *tab, emqx_gm_authz_info_t *info);
+/* emqx_authz_mnesia:purge_rules/0 (:135-141) of this table */
+int emqx_gm_authz_release(emqx_gm_authz *tab);
+
 #ifdef __cplusplus
 }
 #endif

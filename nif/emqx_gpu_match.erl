@@ -14,6 +14,7 @@
          match_batch/2, match_routes_batch/2, fanout_batch/2, empty/1, export_index/1, import_index/1]).
 -export([load_retained/1, load_retained/2, match_retained/3, expire_retained/2]).
 -export([load_shared/3, load_shared/4, pick_shared/4, pick_shared_nif/5]).
+-export([load_authz/1, authorize_batch/2, authz_rule/2, authz_request/3, authorize/5]).
 -export([match/2]).
 
 -on_load(init/0).
@@ -149,6 +150,97 @@ pick_shared(Table, Msgs, Strategy, Seed) ->
 -spec pick_shared_nif(reference(), [binary()], 0..3, [non_neg_integer()], non_neg_integer()) ->
           [[{binary(), {non_neg_integer(), non_neg_integer()}}]] | {error, term()}.
 pick_shared_nif(_Table, _Topics, _Strategy, _Hashes, _Seed) -> erlang:nif_error(nif_not_loaded).
+
+%% The authorization chain (file and built-in-database sources, in order) as
+%% one table in HBM (emqx_gm_authz_build).  Segment = {Kind, [{Key, [Rule]}]}:
+%% Kind 0 one rule list for every client ({<<>>, Rules}: a file source, or the
+%% built-in database's `all` record), 1 / 2 the clientid / username records
+%% (emqx_authz_mnesia.erl:123-132).  Rules come from authz_rule/2.  A table is
+%% immutable: a changed ACL is a new load_authz/1 the caller swaps in.  On a node
+%% with several GPUs the table lives on the first one.
+-spec load_authz([{0..2, [{binary(), [tuple()]}]}]) -> {ok, reference()} | {error, term()}.
+load_authz(_Segments) -> erlang:nif_error(nif_not_loaded).
+
+%% emqx_authz:do_authorize/4 (emqx_authz.erl:307-317) for a window of requests
+%% from authz_request/3, in order: {Verdict, RuleId} with Verdict 0 nomatch
+%% (RuleId 16#FFFFFFFF), 1 allow, 2 deny.  No '$'-rule, as emqx_authz_rule has
+%% none: <<"#">> authorizes <<"$SYS/x">>.
+-spec authorize_batch(reference(), [tuple()]) -> [{0..2, non_neg_integer()}] | {error, term()}.
+authorize_batch(_Table, _Requests) -> erlang:nif_error(nif_not_loaded).
+
+%% A rule of the reference (emqx_authz_rule.erl:49, or {Permission, all}) with
+%% the caller's id, in load_authz/1's form.  Regexes: the K-th distinct {re, _}
+%% of the table (K < 32) is written {username | clientid, {re_bit, K}}; the
+%% caller runs re:run/2 for each of them once per connection and hands the bits
+%% to authz_request/3 as ReMask.
+-spec authz_rule(non_neg_integer(), tuple()) -> tuple().
+authz_rule(Id, {Permission, all}) ->
+    authz_rule(Id, {Permission, all, all, [<<"#">>]});
+authz_rule(Id, {Permission, Who, Action, Topics}) ->
+    {Op, Leaves} = case Who of
+                       all -> {0, []};
+                       {'and', L} -> {0, L};
+                       {'or', L} -> {1, L};
+                       Leaf -> {0, [Leaf]}
+                   end,
+    {Id, perm_code(Permission), action_code(Action), Op,
+     [authz_leaf(X) || X <- Leaves], [authz_filter(T) || T <- Topics]}.
+
+perm_code(allow) -> 1;
+perm_code(deny) -> 2.
+
+action_code(publish) -> 1;
+action_code(subscribe) -> 2;
+action_code(all) -> 3.
+
+authz_leaf({user, U}) -> authz_leaf({username, U});
+authz_leaf({client, C}) -> authz_leaf({clientid, C});
+authz_leaf({_, {re_bit, K}}) -> {3, <<K>>};
+authz_leaf({username, U}) -> {0, iolist_to_binary(U)};
+authz_leaf({clientid, C}) -> {1, iolist_to_binary(C)};
+authz_leaf({ipaddr, CIDR}) -> {2, cidr_bytes(CIDR)};
+authz_leaf({ipaddrs, CIDRs}) -> {2, iolist_to_binary([cidr_bytes(C) || C <- CIDRs])};
+authz_leaf({'and', _}) -> {4, <<>>};   %% nested: refused by the library, as the reference's who() type has none
+authz_leaf({'or', _}) -> {5, <<>>}.
+
+%% esockd_cidr:parse(CIDR, true): family, lo, hi
+cidr_bytes(CIDR) ->
+    {Lo, Hi, _Len} = esockd_cidr:parse(CIDR, true),
+    Fam = case tuple_size(Lo) of 4 -> 4; 8 -> 6 end,
+    <<Fam, (addr_bytes(Lo))/binary, (addr_bytes(Hi))/binary>>.
+
+addr_bytes({A, B, C, D}) -> <<A, B, C, D, 0:96>>;
+addr_bytes(V6) -> << <<W:16>> || W <- tuple_to_list(V6) >>.
+
+authz_filter({eq, T}) -> {1, iolist_to_binary(T)};
+authz_filter(T) ->
+    case iolist_to_binary(T) of
+        <<"eq ", Rest/binary>> -> {1, Rest};
+        Bin -> {0, Bin}
+    end.
+
+%% One request of authorize_batch/2 from the channel's clientinfo.
+-spec authz_request(map(), publish | subscribe, binary()) -> tuple().
+authz_request(ClientInfo, PubSub, Topic) ->
+    Peer = case maps:get(peerhost, ClientInfo, undefined) of
+               undefined -> undefined;
+               {A, B, C, D} -> <<A, B, C, D>>;
+               V6 -> addr_bytes(V6)
+           end,
+    {Topic, maps:get(clientid, ClientInfo, undefined), maps:get(username, ClientInfo, undefined), Peer,
+     action_code(PubSub), maps:get(authz_re_mask, ClientInfo, 0)}.
+
+%% The 'client.authorize' hook's callback with fallback: the verdict of the first
+%% matching rule, DefaultResult on nomatch (authorization.no_match,
+%% emqx_authz.erl:297-304), emqx_authz:authorize/5 on {error, _}.
+-spec authorize(reference(), map(), publish | subscribe, binary(), allow | deny) -> {stop, allow | deny}.
+authorize(Table, ClientInfo, PubSub, Topic, DefaultResult) ->
+    case authorize_batch(Table, [authz_request(ClientInfo, PubSub, Topic)]) of
+        [{1, _}] -> {stop, allow};
+        [{2, _}] -> {stop, deny};
+        [{0, _}] -> {stop, DefaultResult};
+        {error, _} -> emqx_authz:authorize(ClientInfo, PubSub, Topic, DefaultResult, emqx_authz:lookup())
+    end.
 
 %% emqx_trie:match/1 drop-in with fallback.
 -spec match(reference(), binary()) -> [binary()].

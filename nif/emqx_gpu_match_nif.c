@@ -35,10 +35,14 @@ typedef struct {
   emqx_gm_index *idx;
 } gm_shared_res;
 
-static ErlNifResourceType *INDEX_RT, *RETAINED_RT, *SHARED_RT;
+typedef struct {
+  emqx_gm_authz *tab;
+} gm_authz_res;
+
+static ErlNifResourceType *INDEX_RT, *RETAINED_RT, *SHARED_RT, *AUTHZ_RT;
 static emqx_gm_ctx *CTX;
 static ERL_NIF_TERM A_OK, A_ERROR, A_BADARG, A_INSERT, A_DELETE, A_SUBSCRIBE, A_UNSUBSCRIBE, A_ROUTE_ADD,
-    A_ROUTE_DELETE;
+    A_ROUTE_DELETE, A_UNDEFINED;
 
 static void index_dtor(ErlNifEnv *env, void *obj) {
   gm_index_res *r = (gm_index_res *)obj;
@@ -56,6 +60,12 @@ static void shared_dtor(ErlNifEnv *env, void *obj) {
   gm_shared_res *r = (gm_shared_res *)obj;
   (void)env;
   if (r->sh) emqx_gm_shared_release(r->sh);
+}
+
+static void authz_dtor(ErlNifEnv *env, void *obj) {
+  gm_authz_res *r = (gm_authz_res *)obj;
+  (void)env;
+  if (r->tab) emqx_gm_authz_release(r->tab);
 }
 
 /* LoadInfo (erlang:load_nif/2): a device ordinal, or the node's device list
@@ -84,6 +94,8 @@ static int load(ErlNifEnv *env, void **priv, ERL_NIF_TERM info) {
   INDEX_RT = enif_open_resource_type(env, NULL, "emqx_gm_index", index_dtor, ERL_NIF_RT_CREATE, NULL);
   RETAINED_RT = enif_open_resource_type(env, NULL, "emqx_gm_retained", retained_dtor, ERL_NIF_RT_CREATE, NULL);
   SHARED_RT = enif_open_resource_type(env, NULL, "emqx_gm_shared", shared_dtor, ERL_NIF_RT_CREATE, NULL);
+  AUTHZ_RT = enif_open_resource_type(env, NULL, "emqx_gm_authz", authz_dtor, ERL_NIF_RT_CREATE, NULL);
+  A_UNDEFINED = enif_make_atom(env, "undefined");
   A_OK = enif_make_atom(env, "ok");
   A_ERROR = enif_make_atom(env, "error");
   A_BADARG = enif_make_atom(env, "badarg");
@@ -93,7 +105,7 @@ static int load(ErlNifEnv *env, void **priv, ERL_NIF_TERM info) {
   A_UNSUBSCRIBE = enif_make_atom(env, "unsubscribe");
   A_ROUTE_ADD = enif_make_atom(env, "route_add");
   A_ROUTE_DELETE = enif_make_atom(env, "route_delete");
-  return emqx_gm_open(&o, &CTX) == EMQX_GM_OK && INDEX_RT && RETAINED_RT && SHARED_RT ? 0 : 1;
+  return emqx_gm_open(&o, &CTX) == EMQX_GM_OK && INDEX_RT && RETAINED_RT && SHARED_RT && AUTHZ_RT ? 0 : 1;
 }
 
 static void unload(ErlNifEnv *env, void *priv) {
@@ -762,6 +774,252 @@ static ERL_NIF_TERM pick_shared_nif(ErlNifEnv *env, int argc, const ERL_NIF_TERM
   return result;
 }
 
+/* ---- authorization check (emqx_gm_authz_*): emqx_authz:do_authorize/4 over file + built-in-database sources ----
+ * Growable arrays for the flat description / request batch. */
+typedef struct {
+  uint8_t *p;
+  uint64_t n, cap;
+} az_buf;
+
+static void az_put(az_buf *b, const void *src, uint64_t bytes) {
+  if (b->n + bytes + 64 > b->cap) {
+    uint64_t cap = b->cap ? b->cap : 256;
+    uint8_t *q;
+    while (cap < b->n + bytes + 64) cap *= 2;
+    q = enif_alloc(cap);
+    if (b->n) memcpy(q, b->p, b->n);
+    if (b->p) enif_free(b->p);
+    b->p = q;
+    b->cap = cap;
+  }
+  if (bytes) memcpy(b->p + b->n, src, bytes);
+  b->n += bytes;
+}
+static void az_put_u64(az_buf *b, uint64_t v) { az_put(b, &v, 8); }
+static void az_put_u32(az_buf *b, uint32_t v) { az_put(b, &v, 4); }
+static void az_put_u8(az_buf *b, unsigned v) {
+  uint8_t x = (uint8_t)v;
+  az_put(b, &x, 1);
+}
+static void az_free(az_buf *b, int n) {
+  int i;
+  for (i = 0; i < n; ++i)
+    if (b[i].p) enif_free(b[i].p);
+}
+
+/* load_authz([Segment]) -> {ok, Table}
+ * Segment = {Kind, [{Key, [Rule]}]}: Kind 0 a GLOBAL segment (one {<<>>, Rules}: a
+ * file source's rules, or the built-in database's `all` record), 1 / 2 the
+ * clientid / username records (emqx_authz_mnesia.erl:123-132), in chain order.
+ * Rule = {Id, Perm, Action, WhoOp, [{LeafKind, Arg}], [{FilterKind, Filter}]} with
+ * the codes of emqx_gpu_match.h (EMQX_GM_AUTHZ_*); emqx_gpu_match:authz_rule/2
+ * makes one from the reference's rule tuple (emqx_authz_rule.erl:49). */
+enum { AZ_SEG_KIND, AZ_SEG_OFF, AZ_RANGE_OFF, AZ_KEYS, AZ_KEY_OFF, AZ_RULE_ID, AZ_PERM, AZ_ACTION, AZ_OP, AZ_WHO_OFF,
+       AZ_FILT_OFF, AZ_LEAF_KIND, AZ_LEAF_BYTES, AZ_LEAF_OFF, AZ_FILT_KIND, AZ_FILT_BYTES, AZ_FILT_BOFF, AZ_NBUF };
+
+static ERL_NIF_TERM load_authz(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  az_buf b[AZ_NBUF];
+  ERL_NIF_TERM seg, segs = argv[0], h, t, rh, rt, lh, lt, term;
+  const ERL_NIF_TERM *tup, *kt, *ru, *lf;
+  int arity, rc, ok = 1;
+  unsigned kind, u;
+  uint64_t n_segs = 0, n_ranges = 0, n_rules = 0, n_leaves = 0, n_filters = 0;
+  ErlNifBinary bin;
+  emqx_gm_authz_desc d;
+  emqx_gm_authz *tab = NULL;
+  gm_authz_res *res;
+  (void)argc;
+  memset(b, 0, sizeof(b));
+  az_put_u64(&b[AZ_SEG_OFF], 0), az_put_u64(&b[AZ_RANGE_OFF], 0), az_put_u64(&b[AZ_KEY_OFF], 0);
+  az_put_u64(&b[AZ_WHO_OFF], 0), az_put_u64(&b[AZ_FILT_OFF], 0), az_put_u64(&b[AZ_LEAF_OFF], 0);
+  az_put_u64(&b[AZ_FILT_BOFF], 0);
+  az_put(&b[AZ_SEG_KIND], NULL, 0), az_put(&b[AZ_KEYS], NULL, 0), az_put(&b[AZ_RULE_ID], NULL, 0);
+  az_put(&b[AZ_PERM], NULL, 0), az_put(&b[AZ_ACTION], NULL, 0), az_put(&b[AZ_OP], NULL, 0);
+  az_put(&b[AZ_LEAF_KIND], NULL, 0), az_put(&b[AZ_LEAF_BYTES], NULL, 0), az_put(&b[AZ_FILT_KIND], NULL, 0);
+  az_put(&b[AZ_FILT_BYTES], NULL, 0);
+  while (ok && enif_get_list_cell(env, segs, &seg, &segs)) {
+    ok = enif_get_tuple(env, seg, &arity, &tup) && arity == 2 && enif_get_uint(env, tup[0], &kind);
+    if (!ok) break;
+    az_put_u32(&b[AZ_SEG_KIND], kind);
+    ++n_segs;
+    t = tup[1];
+    while (ok && enif_get_list_cell(env, t, &h, &t)) {
+      ok = enif_get_tuple(env, h, &arity, &kt) && arity == 2 && enif_inspect_binary(env, kt[0], &bin);
+      if (!ok) break;
+      az_put(&b[AZ_KEYS], bin.data, bin.size);
+      az_put_u64(&b[AZ_KEY_OFF], b[AZ_KEYS].n);
+      rt = kt[1];
+      while (ok && enif_get_list_cell(env, rt, &rh, &rt)) {
+        ok = enif_get_tuple(env, rh, &arity, &ru) && arity == 6 && enif_get_uint(env, ru[0], &u);
+        if (!ok) break;
+        az_put_u32(&b[AZ_RULE_ID], u);
+        ok = enif_get_uint(env, ru[1], &u);
+        az_put_u8(&b[AZ_PERM], u);
+        ok = ok && enif_get_uint(env, ru[2], &u);
+        az_put_u8(&b[AZ_ACTION], u);
+        ok = ok && enif_get_uint(env, ru[3], &u);
+        az_put_u8(&b[AZ_OP], u);
+        lt = ru[4];
+        while (ok && enif_get_list_cell(env, lt, &lh, &lt)) {
+          ok = enif_get_tuple(env, lh, &arity, &lf) && arity == 2 && enif_get_uint(env, lf[0], &u) &&
+               enif_inspect_binary(env, lf[1], &bin);
+          if (!ok) break;
+          az_put_u8(&b[AZ_LEAF_KIND], u);
+          az_put(&b[AZ_LEAF_BYTES], bin.data, bin.size);
+          az_put_u64(&b[AZ_LEAF_OFF], b[AZ_LEAF_BYTES].n);
+          ++n_leaves;
+        }
+        lt = ru[5];
+        while (ok && enif_get_list_cell(env, lt, &lh, &lt)) {
+          ok = enif_get_tuple(env, lh, &arity, &lf) && arity == 2 && enif_get_uint(env, lf[0], &u) &&
+               enif_inspect_binary(env, lf[1], &bin);
+          if (!ok) break;
+          az_put_u8(&b[AZ_FILT_KIND], u);
+          az_put(&b[AZ_FILT_BYTES], bin.data, bin.size);
+          az_put_u64(&b[AZ_FILT_BOFF], b[AZ_FILT_BYTES].n);
+          ++n_filters;
+        }
+        az_put_u64(&b[AZ_WHO_OFF], n_leaves);
+        az_put_u64(&b[AZ_FILT_OFF], n_filters);
+        ++n_rules;
+      }
+      az_put_u64(&b[AZ_RANGE_OFF], n_rules);
+      ++n_ranges;
+    }
+    az_put_u64(&b[AZ_SEG_OFF], n_ranges);
+  }
+  if (!ok) {
+    az_free(b, AZ_NBUF);
+    return enif_make_badarg(env);
+  }
+  memset(&d, 0, sizeof(d));
+  d.n_segments = (uint32_t)n_segs;
+  d.seg_kind = (const uint32_t *)b[AZ_SEG_KIND].p;
+  d.seg_range_off = (const uint64_t *)b[AZ_SEG_OFF].p;
+  d.n_ranges = n_ranges;
+  d.range_rule_off = (const uint64_t *)b[AZ_RANGE_OFF].p;
+  d.key_bytes = b[AZ_KEYS].p;
+  d.key_off = (const uint64_t *)b[AZ_KEY_OFF].p;
+  d.n_rules = n_rules;
+  d.rule_id = (const uint32_t *)b[AZ_RULE_ID].p;
+  d.rule_perm = b[AZ_PERM].p;
+  d.rule_action = b[AZ_ACTION].p;
+  d.rule_who_op = b[AZ_OP].p;
+  d.rule_who_off = (const uint64_t *)b[AZ_WHO_OFF].p;
+  d.rule_filter_off = (const uint64_t *)b[AZ_FILT_OFF].p;
+  d.n_leaves = n_leaves;
+  d.leaf_kind = b[AZ_LEAF_KIND].p;
+  d.leaf_bytes = b[AZ_LEAF_BYTES].p;
+  d.leaf_off = (const uint64_t *)b[AZ_LEAF_OFF].p;
+  d.n_filters = n_filters;
+  d.filter_kind = b[AZ_FILT_KIND].p;
+  d.filter_bytes = b[AZ_FILT_BYTES].p;
+  d.filter_off = (const uint64_t *)b[AZ_FILT_BOFF].p;
+  rc = emqx_gm_authz_build(CTX, &d, 0, &tab);
+  az_free(b, AZ_NBUF);
+  if (rc != EMQX_GM_OK) return error_tuple(env, rc);
+  res = enif_alloc_resource(AUTHZ_RT, sizeof(*res));
+  res->tab = tab;
+  term = enif_make_resource(env, res);
+  enif_release_resource(res);
+  return enif_make_tuple2(env, A_OK, term);
+}
+
+/* authorize_batch(Table, [{Topic, ClientId, Username, Peerhost, Action, ReMask}]) -> [{Verdict, RuleId}]
+ * emqx_authz:do_authorize/4 (emqx_authz.erl:307-317) per request, in order:
+ * ClientId / Username a binary or `undefined`; Peerhost the address's 4 or 16
+ * bytes or `undefined`; Action 1 publish, 2 subscribe; ReMask the client's regex
+ * bits.  Verdict 0 nomatch (RuleId 16#FFFFFFFF), 1 allow, 2 deny. */
+enum { AQ_TOPICS, AQ_TOFF, AQ_CIDS, AQ_COFF, AQ_UNS, AQ_UOFF, AQ_FLAGS, AQ_PEER, AQ_ACTION, AQ_MASK, AQ_NBUF };
+
+static ERL_NIF_TERM authorize_batch(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_authz_res *r;
+  az_buf b[AQ_NBUF];
+  ERL_NIF_TERM h, t = argv[1], result;
+  const ERL_NIF_TERM *q;
+  int arity, rc, ok = 1;
+  unsigned u;
+  uint64_t n = 0, i;
+  ErlNifBinary bin;
+  emqx_gm_authz_batch batch;
+  uint8_t *verdict, peer[16];
+  uint32_t *rule;
+  (void)argc;
+  if (!enif_get_resource(env, argv[0], AUTHZ_RT, (void **)&r)) return enif_make_badarg(env);
+  memset(b, 0, sizeof(b));
+  az_put_u64(&b[AQ_TOFF], 0), az_put_u64(&b[AQ_COFF], 0), az_put_u64(&b[AQ_UOFF], 0);
+  az_put(&b[AQ_TOPICS], NULL, 0), az_put(&b[AQ_CIDS], NULL, 0), az_put(&b[AQ_UNS], NULL, 0);
+  az_put(&b[AQ_FLAGS], NULL, 0), az_put(&b[AQ_PEER], NULL, 0), az_put(&b[AQ_ACTION], NULL, 0);
+  az_put(&b[AQ_MASK], NULL, 0);
+  while (ok && enif_get_list_cell(env, t, &h, &t)) {
+    unsigned flags = 0;
+    ok = enif_get_tuple(env, h, &arity, &q) && arity == 6 && enif_inspect_binary(env, q[0], &bin);
+    if (!ok) break;
+    az_put(&b[AQ_TOPICS], bin.data, bin.size);
+    az_put_u64(&b[AQ_TOFF], b[AQ_TOPICS].n);
+    if (!enif_is_identical(q[1], A_UNDEFINED)) {
+      ok = enif_inspect_binary(env, q[1], &bin);
+      if (!ok) break;
+      az_put(&b[AQ_CIDS], bin.data, bin.size);
+      flags |= EMQX_GM_AUTHZ_F_CLIENTID;
+    }
+    az_put_u64(&b[AQ_COFF], b[AQ_CIDS].n);
+    if (!enif_is_identical(q[2], A_UNDEFINED)) {
+      ok = enif_inspect_binary(env, q[2], &bin);
+      if (!ok) break;
+      az_put(&b[AQ_UNS], bin.data, bin.size);
+      flags |= EMQX_GM_AUTHZ_F_USERNAME;
+    }
+    az_put_u64(&b[AQ_UOFF], b[AQ_UNS].n);
+    memset(peer, 0, sizeof(peer));
+    if (!enif_is_identical(q[3], A_UNDEFINED)) {
+      ok = enif_inspect_binary(env, q[3], &bin) && (bin.size == 4 || bin.size == 16);
+      if (!ok) break;
+      memcpy(peer, bin.data, bin.size);
+      flags |= EMQX_GM_AUTHZ_F_PEERHOST | (bin.size == 16 ? EMQX_GM_AUTHZ_F_IPV6 : 0u);
+    }
+    az_put(&b[AQ_PEER], peer, 16);
+    az_put_u8(&b[AQ_FLAGS], flags);
+    ok = enif_get_uint(env, q[4], &u);
+    az_put_u8(&b[AQ_ACTION], u);
+    ok = ok && enif_get_uint(env, q[5], &u);
+    az_put_u32(&b[AQ_MASK], u);
+    ++n;
+  }
+  if (!ok) {
+    az_free(b, AQ_NBUF);
+    return enif_make_badarg(env);
+  }
+  memset(&batch, 0, sizeof(batch));
+  batch.n = n;
+  batch.topic_bytes = b[AQ_TOPICS].p;
+  batch.topic_off = (const uint64_t *)b[AQ_TOFF].p;
+  batch.clientid_bytes = b[AQ_CIDS].p;
+  batch.clientid_off = (const uint64_t *)b[AQ_COFF].p;
+  batch.username_bytes = b[AQ_UNS].p;
+  batch.username_off = (const uint64_t *)b[AQ_UOFF].p;
+  batch.flags = b[AQ_FLAGS].p;
+  batch.peerhost = b[AQ_PEER].p;
+  batch.action = b[AQ_ACTION].p;
+  batch.re_mask = (const uint32_t *)b[AQ_MASK].p;
+  verdict = enif_alloc(n ? n : 1);
+  rule = enif_alloc(sizeof(uint32_t) * (n ? n : 1));
+  rc = emqx_gm_authz_check(CTX, r->tab, &batch, 0, verdict, rule);
+  az_free(b, AQ_NBUF);
+  if (rc != EMQX_GM_OK) {
+    enif_free(verdict);
+    enif_free(rule);
+    return error_tuple(env, rc);
+  }
+  result = enif_make_list(env, 0);
+  for (i = n; i > 0; --i)
+    result = enif_make_list_cell(
+        env, enif_make_tuple2(env, enif_make_uint(env, verdict[i - 1]), enif_make_uint(env, rule[i - 1])), result);
+  enif_free(verdict);
+  enif_free(rule);
+  return result;
+}
+
 static ErlNifFunc funcs[] = {
     {"load_index", 1, load_index, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"load_index", 2, load_index, ERL_NIF_DIRTY_JOB_CPU_BOUND},
@@ -782,6 +1040,8 @@ static ErlNifFunc funcs[] = {
     {"load_shared", 3, load_shared, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"load_shared", 4, load_shared, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"pick_shared_nif", 5, pick_shared_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"load_authz", 1, load_authz, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"authorize_batch", 2, authorize_batch, ERL_NIF_DIRTY_JOB_CPU_BOUND},
 };
 
 ERL_NIF_INIT(emqx_gpu_match, funcs, load, NULL, NULL, unload)
