@@ -260,20 +260,26 @@ void DevPool::trim() {
 int sum_filter_lengths(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint32_t* d_ids, uint64_t nnz,
                        uint64_t* out);
 
-}  // namespace gm
-
-#define GM_GUARD_BEGIN try {
-#define GM_GUARD_END(ctx)                                                  \
-  }                                                                        \
-  catch (const std::bad_alloc&) {                                          \
-    return gm::set_err((ctx), EMQX_GM_ENOMEM, "host allocation failed");   \
-  }                                                                        \
-  catch (const std::exception& e) {                                        \
-    return gm::set_err((ctx), EMQX_GM_EINVAL, e.what());                   \
-  }                                                                        \
-  catch (...) {                                                            \
-    return gm::set_err((ctx), EMQX_GM_EINVAL, "unknown error");            \
+int table_upload(emqx_gm_ctx* ctx, const HostBytes& blob, size_t bytes, const char* what, void** dev_base) {
+  GM_HIP(ctx, hipSetDevice(ctx->device));
+  void* d = nullptr;
+  if (hipMalloc(&d, bytes) != hipSuccess) return set_err(ctx, EMQX_GM_ENOMEM, std::string(what) + ": device tables");
+  hipError_t e = hipMemcpyAsync(d, blob.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) {
+    hipFree(d);
+    return set_err(ctx, EMQX_GM_EDEVICE, std::string(what) + ": upload: " + hipGetErrorString(e));
   }
+  *dev_base = d;
+  return EMQX_GM_OK;
+}
+
+void table_free(int device, void* dev_base) {
+  hipSetDevice(device);
+  hipFree(dev_base);
+}
+
+}  // namespace gm
 
 extern "C" {
 

@@ -22,8 +22,6 @@ namespace gm {
 
 namespace {
 
-inline size_t al32(size_t x) { return (x + 31) & ~size_t(31); }
-
 // offsets from 0, ascending, entries under 2 GiB (the boundary carries no byte count)
 int check_off(const char* name, const uint64_t* o, uint64_t n, const void* bytes, std::string* why) {
   if (!o) {
@@ -46,28 +44,11 @@ int check_off(const char* name, const uint64_t* o, uint64_t n, const void* bytes
   return EMQX_GM_OK;
 }
 
-struct Str {
-  const uint8_t* p;
-  uint64_t len;
-  bool operator==(const Str& o) const { return len == o.len && (!len || !std::memcmp(p, o.p, len)); }
-};
-struct StrHash {
-  size_t operator()(const Str& s) const { return hash_word_host(s.p, s.len); }
+struct WordHash {
+  size_t operator()(const WordRef& s) const { return hash_word_host(s.p, s.len); }
 };
 
 const char* const kReserved[AZ_RESERVED_WORDS] = {"", "+", "#", "${clientid}", "${username}"};
-
-// id of the word in the host tables, or NONE
-uint32_t host_word_find(const AzView& v, const uint8_t* p, uint64_t len) {
-  if (len >= DICT_EMPTY_LEN) return NONE;
-  const uint64_t head = word_head_host(p, len);
-  for (uint64_t s = dict_slot(dict_hash_host(p, len), v.dict_mask);; s = (s + 1) & v.dict_mask) {
-    const DictSlot& e = v.dict[s];
-    if (e.len == DICT_EMPTY_LEN) return NONE;
-    if (e.len != len || e.head != head) continue;
-    if (len <= 8 || !std::memcmp(v.arena + v.word_off[e.word] + 8, p + 8, len - 8)) return e.word;
-  }
-}
 
 // the rule range under a key of a keyed segment (empty: no such key)
 void host_key_find(const AzView& v, const AzSeg& sg, const uint8_t* p, uint64_t len, uint32_t* lo, uint32_t* hi) {
@@ -78,7 +59,7 @@ void host_key_find(const AzView& v, const AzSeg& sg, const uint8_t* p, uint64_t 
     const AzKeySlot& e = v.keys[sg.key_lo + s];
     if (e.len == DICT_EMPTY_LEN) return;
     if (e.len != len || e.hash != h || e.head != head) continue;
-    if (len <= 8 || !std::memcmp(v.arena + e.off + 8, p + 8, len - 8)) {
+    if (len <= 8 || !std::memcmp(v.words.arena + e.off + 8, p + 8, len - 8)) {
       *lo = e.r_lo, *hi = e.r_hi;
       return;
     }
@@ -204,10 +185,10 @@ int az_compile(const emqx_gm_authz_desc* d, emqx_gm_authz** out, std::string* wh
     leaves[l] = lf;
   }
   // ---- filters: words interned in first-seen order behind the reserved ids
-  std::unordered_map<Str, uint32_t, StrHash> ids;
-  std::vector<Str> dw;
+  std::unordered_map<WordRef, uint32_t, WordHash> ids;
+  std::vector<WordRef> dw;
   for (uint32_t k = 0; k < AZ_RESERVED_WORDS; ++k) {
-    const Str s{reinterpret_cast<const uint8_t*>(kReserved[k]), std::strlen(kReserved[k])};
+    const WordRef s{reinterpret_cast<const uint8_t*>(kReserved[k]), std::strlen(kReserved[k])};
     ids.emplace(s, k);
     dw.push_back(s);
   }
@@ -227,7 +208,7 @@ int az_compile(const emqx_gm_authz_desc* d, emqx_gm_authz** out, std::string* wh
     uint64_t s = 0;
     for (uint64_t e = 0; e <= len; ++e)
       if (e == len || p[e] == '/') {
-        const Str w{p + s, e - s};
+        const WordRef w{p + s, e - s};
         auto it = ids.find(w);
         if (it == ids.end()) {
           it = ids.emplace(w, uint32_t(dw.size())).first;
@@ -247,7 +228,7 @@ int az_compile(const emqx_gm_authz_desc* d, emqx_gm_authz** out, std::string* wh
     filters[f] = AzFilter{uint32_t(w_lo), uint32_t(n) | (k << 30)};
   }
   uint64_t word_bytes = 0;
-  for (const Str& w : dw) word_bytes += w.len;
+  for (const WordRef& w : dw) word_bytes += w.len;
   // ---- segments and key tables
   std::vector<AzSeg> segs(d->n_segments);
   std::vector<AzKeySlot> keys;
@@ -306,8 +287,7 @@ int az_compile(const emqx_gm_authz_desc* d, emqx_gm_authz** out, std::string* wh
     return EMQX_GM_EINVAL;
   }
   // ---- the blob
-  uint64_t dict_cap = 16;
-  while (dict_cap < 2 * dw.size()) dict_cap <<= 1;
+  const uint64_t dict_cap = dict_capacity(dw.size());
   size_t o[10];
   size_t at = 0;
   o[0] = at, at = al32(at + (segs.size() + 1) * sizeof(AzSeg));
@@ -342,18 +322,8 @@ int az_compile(const emqx_gm_authz_desc* d, emqx_gm_authz** out, std::string* wh
   auto* dict = reinterpret_cast<DictSlot*>(base + o[7]);
   auto* woff = reinterpret_cast<uint32_t*>(base + o[8]);
   uint8_t* arena = base + o[9];
-  for (uint64_t s = 0; s < dict_cap; ++s) dict[s] = DictSlot{0, DICT_EMPTY_LEN, 0};
-  uint64_t ab = 0;
-  for (uint64_t w = 0; w < dw.size(); ++w) {
-    woff[w] = uint32_t(ab);
-    if (dw[w].len) std::memcpy(arena + ab, dw[w].p, dw[w].len);
-    ab += dw[w].len;
-    uint64_t s = dict_slot(dict_hash_host(dw[w].p, dw[w].len), dict_cap - 1);
-    while (dict[s].len != DICT_EMPTY_LEN) s = (s + 1) & (dict_cap - 1);
-    dict[s] = DictSlot{word_head_host(dw[w].p, dw[w].len), uint32_t(dw[w].len), uint32_t(w)};
-  }
-  woff[dw.size()] = uint32_t(ab);
-  put(o[9] + ab, tail.data(), tail.size());
+  dict_fill(dw.data(), dw.size(), dict, dict_cap, woff, arena);
+  put(o[9] + word_bytes, tail.data(), tail.size());
   t->bytes = at;
   AzView& v = t->hv;
   v.segs = reinterpret_cast<const AzSeg*>(base + o[0]);
@@ -363,10 +333,7 @@ int az_compile(const emqx_gm_authz_desc* d, emqx_gm_authz** out, std::string* wh
   v.filters = reinterpret_cast<const AzFilter*>(base + o[4]);
   v.fwords = reinterpret_cast<const uint32_t*>(base + o[5]);
   v.keys = reinterpret_cast<const AzKeySlot*>(base + o[6]);
-  v.dict = dict;
-  v.word_off = woff;
-  v.arena = arena;
-  v.dict_mask = dict_cap - 1;
+  v.words = DictView{dict, woff, arena, dict_cap - 1};
   v.n_segs = d->n_segments;
   v.n_rules = uint32_t(d->n_rules);
   v.n_words = uint32_t(dw.size());
@@ -475,9 +442,9 @@ bool host_rule_match(const AzView& v, const HostReq& q, uint32_t r) {
     const AzLeaf& lf = v.leaves[l];
     bool m = false;
     if (lf.kind == EMQX_GM_AUTHZ_WHO_USERNAME)
-      m = q.has_un && q.un_len == lf.b && (!lf.b || !std::memcmp(q.un, v.arena + lf.a, lf.b));
+      m = q.has_un && q.un_len == lf.b && (!lf.b || !std::memcmp(q.un, v.words.arena + lf.a, lf.b));
     else if (lf.kind == EMQX_GM_AUTHZ_WHO_CLIENTID)
-      m = q.has_cid && q.cid_len == lf.b && (!lf.b || !std::memcmp(q.cid, v.arena + lf.a, lf.b));
+      m = q.has_cid && q.cid_len == lf.b && (!lf.b || !std::memcmp(q.cid, v.words.arena + lf.a, lf.b));
     else if (lf.kind == EMQX_GM_AUTHZ_WHO_IPADDR) {
       for (uint32_t c = 0; c < lf.b && !m && q.has_peer; ++c) m = az_cidr_match(v.cidrs[lf.a + c], q.peer, q.v6);
     } else
@@ -515,7 +482,7 @@ void az_check_host(const emqx_gm_authz* t, const emqx_gm_authz_batch* b, uint8_t
     for (uint64_t e = 0; e <= len; ++e)
       if (e == len || p[e] == '/') {
         const uint64_t wl = e - s;
-        const uint32_t id = host_word_find(v, p + s, wl);
+        const uint32_t id = dict_find_host(v.words, p + s, wl);
         q.w.push_back(id);
         // feed_var/3: the value as one binary word, or the placeholder's own text when undefined
         const bool bin = az_is_binary_word(p + s, uint32_t(std::min<uint64_t>(wl, 0x7FFFFFFF)));
@@ -551,36 +518,23 @@ void az_check_host(const emqx_gm_authz* t, const emqx_gm_authz_batch* b, uint8_t
 
 }  // namespace gm
 
-#define AZ_GUARD_BEGIN try {
-#define AZ_GUARD_END(ctx)                                                \
-  }                                                                      \
-  catch (const std::bad_alloc&) {                                        \
-    return gm::set_err((ctx), EMQX_GM_ENOMEM, "host allocation failed"); \
-  }                                                                      \
-  catch (const std::exception& e) {                                      \
-    return gm::set_err((ctx), EMQX_GM_EINVAL, e.what());                 \
-  }                                                                      \
-  catch (...) {                                                          \
-    return gm::set_err((ctx), EMQX_GM_EINVAL, "unknown error");          \
-  }
-
 extern "C" {
 
 int emqx_gm_authz_compile_host(const emqx_gm_authz_desc* desc, emqx_gm_authz** out) {
   if (!out) return EMQX_GM_EINVAL;
   *out = nullptr;
-  AZ_GUARD_BEGIN
+  GM_GUARD_BEGIN
   std::string why;
   const int rc = gm::az_compile(desc, out, &why);
   return rc ? gm::set_err(nullptr, rc, "authz_build: " + why) : rc;
-  AZ_GUARD_END(nullptr)
+  GM_GUARD_END(nullptr)
 }
 
 int emqx_gm_authz_build(emqx_gm_ctx* ctx, const emqx_gm_authz_desc* desc, uint32_t flags, emqx_gm_authz** out) {
   if (!ctx || !out) return EMQX_GM_EINVAL;
   *out = nullptr;
   if (flags) return gm::set_err(ctx, EMQX_GM_EINVAL, "authz_build: flags");
-  AZ_GUARD_BEGIN
+  GM_GUARD_BEGIN
   const auto t0 = std::chrono::steady_clock::now();
   std::string why;
   emqx_gm_authz* t = nullptr;
@@ -595,7 +549,7 @@ int emqx_gm_authz_build(emqx_gm_ctx* ctx, const emqx_gm_authz_desc* desc, uint32
   t->info.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   *out = t;
   return EMQX_GM_OK;
-  AZ_GUARD_END(ctx)
+  GM_GUARD_END(ctx)
 }
 
 int emqx_gm_authz_check(emqx_gm_ctx* ctx, const emqx_gm_authz* tab, const emqx_gm_authz_batch* batch, uint32_t flags,
@@ -604,7 +558,7 @@ int emqx_gm_authz_check(emqx_gm_ctx* ctx, const emqx_gm_authz* tab, const emqx_g
   if (flags & ~EMQX_GM_AUTHZ_TIMED) return gm::set_err(ctx, EMQX_GM_EINVAL, "authz_check: flags");
   if (!tab->dev_base) return gm::set_err(ctx, EMQX_GM_EUNSUPPORTED, "authz_check: a host-only table");
   if (tab->device != ctx->device) return gm::set_err(ctx, EMQX_GM_EINVAL, "authz_check: the table is on another device");
-  AZ_GUARD_BEGIN
+  GM_GUARD_BEGIN
   std::string why;
   if (const int rc = gm::az_check_batch(batch, &why)) return gm::set_err(ctx, rc, "authz_check: " + why);
   if (!batch->n) return EMQX_GM_OK;
@@ -612,20 +566,20 @@ int emqx_gm_authz_check(emqx_gm_ctx* ctx, const emqx_gm_authz* tab, const emqx_g
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return gm::az_check_device(ctx, const_cast<emqx_gm_authz*>(tab), batch, (flags & EMQX_GM_AUTHZ_TIMED) != 0, verdict,
                              rule);
-  AZ_GUARD_END(ctx)
+  GM_GUARD_END(ctx)
 }
 
 int emqx_gm_authz_check_host(const emqx_gm_authz* tab, const emqx_gm_authz_batch* batch, uint8_t* verdict,
                              uint32_t* rule) {
   if (!tab || !batch) return EMQX_GM_EINVAL;
-  AZ_GUARD_BEGIN
+  GM_GUARD_BEGIN
   std::string why;
   if (const int rc = gm::az_check_batch(batch, &why)) return gm::set_err(nullptr, rc, "authz_check_host: " + why);
   if (!batch->n) return EMQX_GM_OK;
   if (!verdict || !rule) return gm::set_err(nullptr, EMQX_GM_EINVAL, "authz_check_host: NULL result");
   gm::az_check_host(tab, batch, verdict, rule);
   return EMQX_GM_OK;
-  AZ_GUARD_END(nullptr)
+  GM_GUARD_END(nullptr)
 }
 
 int emqx_gm_authz_info(const emqx_gm_authz* tab, emqx_gm_authz_info_t* info) {

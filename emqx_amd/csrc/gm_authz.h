@@ -91,10 +91,7 @@ struct AzView {
   const AzFilter* filters;
   const uint32_t* fwords;
   const AzKeySlot* keys;
-  const DictSlot* dict;
-  const uint32_t* word_off;  // [n_words + 1]
-  const uint8_t* arena;      // word bytes in id order, then key and leaf-value bytes
-  uint64_t dict_mask;
+  DictView words;  // filter word -> id (gm_dict.h); its arena: word bytes in id order, then key and leaf-value bytes
   uint32_t n_segs, n_rules, n_words, pad;
 };
 

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "gm_authz.h"
+#include "gm_device.h"
 
 namespace gm {
 namespace {
@@ -48,53 +49,22 @@ struct AzBatchDev {
   uint32_t n;
 };
 
-__device__ __forceinline__ bool bytes_eq(const uint8_t* a, const uint8_t* b, uint32_t n) {
-  uint32_t k = 0;
-  while (k < n && a[k] == b[k]) ++k;
-  return k == n;
-}
-
-__device__ __forceinline__ uint32_t az_hash(const uint8_t* p, uint32_t len, uint64_t* head_out) {
-  uint32_t h = DICT_HASH_SEED;
-  uint64_t head = 0;
-  for (uint32_t i = 0; i < len; i += 8) {
-    uint64_t c = 0;
-    for (uint32_t k = 0; k < 8 && i + k < len; ++k) c |= uint64_t(p[i + k]) << (8 * k);
-    if (!i) head = c;
-    h = dict_hash_step(h, c);
-  }
-  *head_out = head;
-  return dict_hash_final(h, len);
-}
-
-// id of the word p[0, len) in the table's dictionary, or NONE (hits verified by bytes)
-__device__ uint32_t az_word_find(const AzView& v, const uint8_t* p, uint32_t len) {
-  uint64_t head;
-  const uint32_t h = az_hash(p, len, &head);
-  for (uint64_t s = dict_slot(h, v.dict_mask);; s = (s + 1) & v.dict_mask) {
-    const DictSlot e = v.dict[s];
-    if (e.len == DICT_EMPTY_LEN) return NONE;
-    if (e.len != len || e.head != head) continue;
-    if (len <= 8 || bytes_eq(v.arena + v.word_off[e.word] + 8, p + 8, len - 8)) return e.word;
-  }
-}
-
 // the slot of a key in a keyed segment's table (absolute index), or NONE.  The
 // rule range is read from the slot afterwards, by the caller: the lookup hands
-// back one value, as az_word_find does.  (With the range written through two
+// back one value, as dict_find (gm_device.h) does.  (With the range written through two
 // out-parameters inside this loop, the gfx950 code lost it for every key longer
 // than 8 bytes: after the tail compare the registers holding it were restored
 // to the "no key" values.  tests/test_gpu_authz.py covers key lengths 0-255.)
 __device__ uint32_t az_key_find(const AzView& v, const AzSeg& sg, const uint8_t* p, uint32_t len) {
   uint64_t head;
-  const uint32_t h = az_hash(p, len, &head);
+  const uint32_t h = dict_hash_bytes(p, len, &head);
   for (uint32_t s = h & sg.key_mask;; s = (s + 1) & sg.key_mask) {
     const uint32_t at = sg.key_lo + s;
     const AzKeySlot* e = v.keys + at;
     const uint32_t elen = e->len;
     if (elen == DICT_EMPTY_LEN) return NONE;
     if (elen != len || e->hash != h || e->head != head) continue;
-    if (len <= 8 || bytes_eq(v.arena + e->off + 8, p + 8, len - 8)) return at;
+    if (len <= 8 || bytes_eq(v.words.arena + e->off + 8, p + 8, len - 8)) return at;
   }
 }
 
@@ -146,8 +116,8 @@ __device__ bool az_filter_bytes(const AzView& v, const uint32_t* fw, uint32_t n,
       } else if (kind == AZ_F_PATTERN && f == AZ_W_PH_USERNAME && q.has_un) {
         eq = az_is_value(q.p + pos, wl, q.un, q.ulen);
       } else {
-        const uint32_t a = v.word_off[f];
-        eq = wl == v.word_off[f + 1] - a && bytes_eq(q.p + pos, v.arena + a, wl);
+        const uint32_t a = v.words.word_off[f];
+        eq = wl == v.words.word_off[f + 1] - a && bytes_eq(q.p + pos, v.words.arena + a, wl);
       }
       if (eq || (kind != AZ_F_EQ && f == AZ_W_PLUS)) {
         have = e < q.len;
@@ -171,9 +141,9 @@ __device__ __forceinline__ bool az_rule_match(const AzView& v, uint32_t r, const
     const AzLeaf lf = v.leaves[l];
     bool m = false;
     if (lf.kind == EMQX_GM_AUTHZ_WHO_USERNAME) {
-      m = q.has_un && q.ulen == lf.b && bytes_eq(q.un, v.arena + lf.a, lf.b);
+      m = q.has_un && q.ulen == lf.b && bytes_eq(q.un, v.words.arena + lf.a, lf.b);
     } else if (lf.kind == EMQX_GM_AUTHZ_WHO_CLIENTID) {
-      m = q.has_cid && q.clen == lf.b && bytes_eq(q.cid, v.arena + lf.a, lf.b);
+      m = q.has_cid && q.clen == lf.b && bytes_eq(q.cid, v.words.arena + lf.a, lf.b);
     } else if (lf.kind == EMQX_GM_AUTHZ_WHO_IPADDR) {
       if (q.has_peer)
         for (uint32_t c = 0; c < lf.b && !m; ++c) m = az_cidr_match(v.cidrs[lf.a + c], q.peer, q.v6);
@@ -217,7 +187,7 @@ __global__ __launch_bounds__(AZ_BLOCK) void k_authz_check(AzView v, AzBatchDev b
       if (e == q.len || q.p[e] == '/') {
         if (q.L < AZ_LEVELS) {
           const uint32_t wl = e - s;
-          const uint32_t id = az_word_find(v, q.p + s, wl);
+          const uint32_t id = dict_find(v.words, q.p + s, wl);
           col[q.L * AZ_BLOCK] = id;
           // feed_var/3: the value as one binary word, or the placeholder's own text when undefined
           const bool ic = q.has_cid ? az_is_value(q.p + s, wl, q.cid, q.clen) : id == AZ_W_PH_CLIENTID;
@@ -267,62 +237,32 @@ __global__ __launch_bounds__(AZ_BLOCK) void k_authz_check(AzView v, AzBatchDev b
   }
 }
 
-inline size_t al16(size_t x) { return (x + 15) & ~size_t(15); }
-
-struct PinBuf {
-  PinPool* pool;
-  void* p;
-  PinBuf(PinPool* pl, size_t bytes) : pool(pl), p(pl->get(bytes)) {}
-  ~PinBuf() {
-    if (p) pool->put(p);
-  }
-};
-
-struct Events {
-  hipEvent_t e[2] = {};
-  ~Events() {
-    for (hipEvent_t x : e)
-      if (x) hipEventDestroy(x);
-  }
-};
-
 constexpr uint64_t AZ_CHUNK_REQS = 1ull << 20;   // requests of one device round trip
 constexpr uint64_t AZ_CHUNK_BYTES = 1ull << 30;  // ... and the bytes of each of its three text columns (u32 offsets)
 
 }  // namespace
 
 int az_upload(emqx_gm_ctx* ctx, emqx_gm_authz* t) {
-  GM_HIP(ctx, hipSetDevice(ctx->device));
-  void* d = nullptr;
-  if (hipMalloc(&d, t->bytes) != hipSuccess) return set_err(ctx, EMQX_GM_ENOMEM, "authz_build: device tables");
-  hipError_t e = hipMemcpyAsync(d, t->blob.data(), t->bytes, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    hipFree(d);
-    return set_err(ctx, EMQX_GM_EDEVICE, std::string("authz_build: upload: ") + hipGetErrorString(e));
-  }
-  const uint8_t* hb = t->blob.data();
-  uint8_t* db = static_cast<uint8_t*>(d);
-  auto reb = [&](const void* p) { return db + (static_cast<const uint8_t*>(p) - hb); };
-  t->dv.segs = reinterpret_cast<const AzSeg*>(reb(t->hv.segs));
-  t->dv.rules = reinterpret_cast<const AzRule*>(reb(t->hv.rules));
-  t->dv.leaves = reinterpret_cast<const AzLeaf*>(reb(t->hv.leaves));
-  t->dv.cidrs = reinterpret_cast<const AzCidr*>(reb(t->hv.cidrs));
-  t->dv.filters = reinterpret_cast<const AzFilter*>(reb(t->hv.filters));
-  t->dv.fwords = reinterpret_cast<const uint32_t*>(reb(t->hv.fwords));
-  t->dv.keys = reinterpret_cast<const AzKeySlot*>(reb(t->hv.keys));
-  t->dv.dict = reinterpret_cast<const DictSlot*>(reb(t->hv.dict));
-  t->dv.word_off = reinterpret_cast<const uint32_t*>(reb(t->hv.word_off));
-  t->dv.arena = reb(t->hv.arena);
-  t->dev_base = d;
+  if (const int rc = table_upload(ctx, t->blob, t->bytes, "authz_build", &t->dev_base)) return rc;
+  const AzView& h = t->hv;
+  const void* hb = t->blob.data();
+  void* db = t->dev_base;
+  t->dv.segs = rebase(h.segs, hb, db);
+  t->dv.rules = rebase(h.rules, hb, db);
+  t->dv.leaves = rebase(h.leaves, hb, db);
+  t->dv.cidrs = rebase(h.cidrs, hb, db);
+  t->dv.filters = rebase(h.filters, hb, db);
+  t->dv.fwords = rebase(h.fwords, hb, db);
+  t->dv.keys = rebase(h.keys, hb, db);
+  t->dv.words = DictView{rebase(h.words.dict, hb, db), rebase(h.words.word_off, hb, db), rebase(h.words.arena, hb, db),
+                         h.words.dict_mask};
   t->device = ctx->device;
   t->info.device_bytes = t->bytes;
   return EMQX_GM_OK;
 }
 
 void az_free_device(emqx_gm_authz* t) {
-  hipSetDevice(t->device);
-  hipFree(t->dev_base);  // (waits for the device: no queued check still reads the tables)
+  table_free(t->device, t->dev_base);  // (waits for the device: no queued check still reads the tables)
   t->dev_base = nullptr;
 }
 
@@ -380,9 +320,9 @@ static int az_check_chunk(emqx_gm_ctx* ctx, emqx_gm_authz* t, const emqx_gm_auth
   db.rule = reinterpret_cast<uint32_t*>(dout + out_rule);
   db.verdict = dout + out_verdict;
   db.n = uint32_t(m);
-  Events ev;
+  EventSet<2> ev;
   if (timed) {
-    for (hipEvent_t& x : ev.e) GM_HIP(ctx, hipEventCreate(&x));
+    if (const int rc = ev.create(ctx)) return rc;
     GM_HIP(ctx, hipEventRecord(ev.e[0], st));
   }
   hipLaunchKernelGGL(k_authz_check, dim3(uint32_t((m + AZ_BLOCK - 1) / AZ_BLOCK)), dim3(AZ_BLOCK), 0, st, t->dv, db);

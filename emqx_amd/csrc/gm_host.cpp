@@ -821,13 +821,7 @@ int run_host_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb
   const bool use32 = lng != 0 || env_u64("GM_HOST_OFF32", 0) != 0;
   const uint64_t b0 = n ? to[0] : 0, nbytes = n ? to[n] - b0 : 0;
   const bool direct = nbytes > kMappedMax && host_pinned_range(tb + b0, nbytes);
-  struct Pin {
-    PinPool* pool;
-    void* p = nullptr;
-    ~Pin() {
-      if (p) pool->put(p);
-    }
-  } pin{ctx->pins};
+  PinBuf pin(ctx->pins);
   const size_t lbytes = use32 ? (n + 1) * 4 : n * 2 + 2;
   const size_t o_len = direct ? 0 : (nbytes + 64 + 255) & ~size_t(255);  // the lengths' offset in the input
   const size_t in_bytes = (o_len + lbytes + 15) & ~size_t(15), obytes = (n + 1) * 8;
@@ -1037,13 +1031,7 @@ int run_fanout_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_i
     if (m->ids[i] >= nf) return set_err(ctx, EMQX_GM_EINVAL, "fanout: filter id out of range");
   const size_t obytes = (n + 1) * 8, o_ids = (obytes + 15) & ~size_t(15);
   const size_t in_bytes = (o_ids + nnz * 4 + 15) & ~size_t(15);
-  struct Pin {
-    PinPool* pool;
-    void* p = nullptr;
-    ~Pin() {
-      if (p) pool->put(p);
-    }
-  } pin{ctx->pins};
+  PinBuf pin(ctx->pins);
   // ---- under the lock: rows up, the deliveries into a speculative capacity
   // (this context's recent deliveries per match x1.25, a power of two: the
   // result buffers come back from the host pool's cache), the result's

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <map>
 #include <mutex>
+#include <new>
 #include <set>
 #include <string>
 #include <functional>
@@ -16,6 +17,7 @@
 #include "../../include/emqx_gpu_match.h"
 #include "../../include/emqx_gm_ext.h"
 #include "gm_common.h"
+#include "gm_dict.h"
 #include "gm_filters.h"
 
 namespace gm {
@@ -139,6 +141,23 @@ struct PoolBuf {
   }
   template <class T> T* as() const { return static_cast<T*>(p); }
 };
+
+// RAII handle on a page-locked staging buffer of a PinPool (empty until get()).
+struct PinBuf {
+  PinPool* pool;
+  void* p = nullptr;
+  explicit PinBuf(PinPool* pl) : pool(pl) {}
+  PinBuf(PinPool* pl, size_t bytes) : pool(pl), p(pl->get(bytes)) {}
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() {
+    if (p) pool->put(p);
+  }
+};
+
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) & ~(a - 1); }  // a: a power of two
+inline size_t al16(size_t x) { return align_up(x, 16); }
+inline size_t al32(size_t x) { return align_up(x, 32); }
 
 // Per-call scratch sizes of the match pipeline.
 constexpr int FAST_FC = 8;    // frontier capacity per lane (LDS)
@@ -636,3 +655,88 @@ int run_fanout_multi(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_c
       return gm::set_err((ctx), EMQX_GM_EDEVICE,                                              \
                          std::string(#expr) + ": " + hipGetErrorString(_e));                  \
   } while (0)
+
+// The extern "C" entry points let no exception out: GM_GUARD_BEGIN ... GM_GUARD_END(ctx).
+#define GM_GUARD_BEGIN try {
+#define GM_GUARD_END(ctx)                                                  \
+  }                                                                        \
+  catch (const std::bad_alloc&) {                                          \
+    return gm::set_err((ctx), EMQX_GM_ENOMEM, "host allocation failed");   \
+  }                                                                        \
+  catch (const std::exception& e) {                                        \
+    return gm::set_err((ctx), EMQX_GM_EINVAL, e.what());                   \
+  }                                                                        \
+  catch (...) {                                                            \
+    return gm::set_err((ctx), EMQX_GM_EINVAL, "unknown error");            \
+  }
+
+namespace gm {
+
+// N events of one call, destroyed with it; `on` once create() made them all
+template <int N> struct EventSet {
+  hipEvent_t e[N] = {};
+  bool on = false;
+  int create(emqx_gm_ctx* ctx) {
+    for (hipEvent_t& x : e) GM_HIP(ctx, hipEventCreate(&x));
+    on = true;
+    return EMQX_GM_OK;
+  }
+  ~EventSet() {
+    for (hipEvent_t x : e)
+      if (x) hipEventDestroy(x);
+  }
+};
+
+// ---- the side tables (gm_retained / gm_shared / gm_authz): one blob compiled
+// on the host, one device allocation holding a copy of it, a view over each.
+// gm_api.cpp: table_upload copies the blob's first `bytes` bytes into a fresh
+// allocation on ctx's device (*dev_base, set on success; errors read
+// "<what>: device tables" and "<what>: upload: <hip error>"); table_free waits
+// for the device, so no queued kernel still reads the tables.
+int table_upload(emqx_gm_ctx* ctx, const HostBytes& blob, size_t bytes, const char* what, void** dev_base);
+void table_free(int device, void* dev_base);
+// a pointer into the host blob as the same place of the device allocation
+template <class T> T* rebase(T* p, const void* host_base, void* dev_base) {
+  return reinterpret_cast<T*>(static_cast<uint8_t*>(dev_base) +
+                              (reinterpret_cast<const uint8_t*>(p) - static_cast<const uint8_t*>(host_base)));
+}
+
+// a batch of n byte strings b[o[i], o[i + 1]): fewer than 2^32 - 1 of them, ascending, each under 2 GiB
+inline int check_offsets(const uint8_t* b, const uint64_t* o, uint64_t n, std::string* why) {
+  if (n >= 0xFFFFFFFFull) {
+    *why = "more than 2^32 - 2 entries";
+    return EMQX_GM_EINVAL;
+  }
+  if (!o || (!b && n && o[n])) {
+    *why = "NULL buffer";
+    return EMQX_GM_EINVAL;
+  }
+  for (uint64_t i = 0; i < n; ++i)
+    if (o[i + 1] < o[i] || o[i + 1] - o[i] >= (1ull << 31)) {
+      *why = "offsets not ascending (or an entry of 2 GiB) at " + std::to_string(i);
+      return EMQX_GM_EINVAL;
+    }
+  return EMQX_GM_OK;
+}
+
+// a host walk's rows as a malloc'ed CSR (EMQX_GM_ENOMEM: the caller frees what was made), and its release
+inline int csr_to_malloc(const std::vector<uint64_t>& row_off, const std::vector<uint32_t>& ids, emqx_gm_csr* out) {
+  const uint64_t n = row_off.size() - 1;
+  out->row_off = static_cast<uint64_t*>(malloc((n + 1) * 8));
+  out->ids = static_cast<uint32_t*>(malloc(std::max<size_t>(ids.size(), 1) * 4));
+  if (!out->row_off || !out->ids) return EMQX_GM_ENOMEM;
+  std::memcpy(out->row_off, row_off.data(), (n + 1) * 8);
+  if (!ids.empty()) std::memcpy(out->ids, ids.data(), ids.size() * 4);
+  out->n_rows = n;
+  out->nnz = ids.size();
+  return EMQX_GM_OK;
+}
+inline int csr_free_malloc(emqx_gm_csr* csr) {
+  if (!csr) return EMQX_GM_EINVAL;
+  free(csr->row_off);
+  free(csr->ids);
+  std::memset(csr, 0, sizeof(*csr));
+  return EMQX_GM_OK;
+}
+
+}  // namespace gm

@@ -171,13 +171,7 @@ struct Patcher {
 
   // ---- word dictionary (dict_resolve's rules: length + head, tail against the arena)
   uint32_t dict_find(const uint8_t* w, uint64_t len) {
-    const uint64_t head = word_head_host(w, len);
-    for (uint64_t s = dict_slot(dict_hash_host(w, len), v.dict_mask);; s = (s + 1) & v.dict_mask) {
-      const DictSlot& d = dict()[s];
-      if (d.len == DICT_EMPTY_LEN) return NONE;
-      if (d.len == len && d.head == head && (len <= 8 || std::memcmp(arena() + d.word + 8, w + 8, len - 8) == 0))
-        return d.word;
-    }
+    return dict_find_host(DictView{dict(), nullptr, arena(), v.dict_mask}, w, len);  // (a word id is its arena offset)
   }
   uint32_t word(const uint8_t* w, uint64_t len) {
     uint32_t id = dict_find(w, len);
@@ -189,9 +183,7 @@ struct Patcher {
     if (len) std::memcpy(arena() + id, w, len);
     else arena()[id] = 0;
     M.arena_n += own;
-    uint64_t s = dict_slot(dict_hash_host(w, len), v.dict_mask);
-    while (dict()[s].len != DICT_EMPTY_LEN) s = (s + 1) & v.dict_mask;
-    W(dict()[s]) = DictSlot{word_head_host(w, len), uint32_t(len), id};
+    W(dict_vacancy_host(dict(), v.dict_mask, w, len)) = dict_entry_host(w, len, id);
     ++M.dict_used;
     return id;
   }

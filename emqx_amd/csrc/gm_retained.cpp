@@ -19,33 +19,6 @@ namespace gm {
 
 namespace {
 
-struct WordRef {
-  const uint8_t* p;
-  uint64_t len;
-};
-inline bool word_less(const WordRef& a, const WordRef& b) {
-  const uint64_t m = std::min(a.len, b.len);
-  const int c = m ? std::memcmp(a.p, b.p, m) : 0;
-  return c ? c < 0 : a.len < b.len;
-}
-inline bool word_eq(const WordRef& a, const WordRef& b) {
-  return a.len == b.len && (!a.len || !std::memcmp(a.p, b.p, a.len));
-}
-
-inline size_t al16(size_t x) { return (x + 15) & ~size_t(15); }
-
-// id of the word in the host tables, or NONE
-uint32_t host_word_find(const RetView& v, const uint8_t* p, uint64_t len) {
-  if (len >= DICT_EMPTY_LEN) return NONE;
-  const uint64_t head = word_head_host(p, len);
-  for (uint64_t s = dict_slot(dict_hash_host(p, len), v.dict_mask);; s = (s + 1) & v.dict_mask) {
-    const DictSlot& e = v.dict[s];
-    if (e.len == DICT_EMPTY_LEN) return NONE;
-    if (e.len != len || e.head != head) continue;
-    if (len <= 8 || !std::memcmp(v.arena + v.word_off[e.word] + 8, p + 8, len - 8)) return e.word;
-  }
-}
-
 // the child of `parent` through word id w: a binary search over its contiguous, ascending children
 uint32_t host_child(const RetView& v, uint32_t parent, uint32_t w) {
   uint32_t a = v.nodes[parent].child_lo, b = v.nodes[parent + 1].child_lo;
@@ -62,12 +35,10 @@ void set_views(emqx_gm_retained* r, const size_t* o, uint64_t dict_cap) {
   auto fill = [&](RetView& v, uint8_t* base) {
     v.nodes = reinterpret_cast<const RetNode*>(base + o[0]);
     v.depth_ends = reinterpret_cast<const uint32_t*>(base + o[1]);
-    v.dict = reinterpret_cast<const DictSlot*>(base + o[2]);
-    v.word_off = reinterpret_cast<const uint32_t*>(base + o[3]);
-    v.arena = base + o[4];
+    v.words = DictView{reinterpret_cast<const DictSlot*>(base + o[2]), reinterpret_cast<const uint32_t*>(base + o[3]),
+                       base + o[4], dict_cap - 1};
     v.ids = reinterpret_cast<const uint32_t*>(base + o[5]);
     v.expiry = reinterpret_cast<uint64_t*>(base + o[6]);
-    v.dict_mask = dict_cap - 1;
   };
   fill(r->hv, r->blob.data());
   r->dv = r->hv;  // (ret_upload rebases the pointers onto the device allocation)
@@ -75,26 +46,9 @@ void set_views(emqx_gm_retained* r, const size_t* o, uint64_t dict_cap) {
 
 }  // namespace
 
-int ret_check_batch(const uint8_t* b, const uint64_t* o, uint64_t n, std::string* why) {
-  if (n >= 0xFFFFFFFFull) {
-    *why = "more than 2^32 - 2 entries";
-    return EMQX_GM_EINVAL;
-  }
-  if (!o || (!b && n && o[n])) {
-    *why = "NULL buffer";
-    return EMQX_GM_EINVAL;
-  }
-  for (uint64_t i = 0; i < n; ++i)
-    if (o[i + 1] < o[i] || o[i + 1] - o[i] >= (1ull << 31)) {
-      *why = "offsets not ascending (or an entry of 2 GiB) at " + std::to_string(i);
-      return EMQX_GM_EINVAL;
-    }
-  return EMQX_GM_OK;
-}
-
 int ret_compile(const uint8_t* tb, const uint64_t* to, uint64_t n, const uint32_t* ids, const uint64_t* expiry,
                 emqx_gm_retained** out, std::string* why) {
-  if (const int rc = ret_check_batch(tb, to, n, why)) return rc;
+  if (const int rc = check_offsets(tb, to, n, why)) return rc;
   // 1. words of every topic (emqx_topic:words/1: split on '/', empty words kept)
   std::vector<uint64_t> wo(n + 1, 0);  // topic -> its first word in `words`
   std::vector<WordRef> words;
@@ -213,8 +167,7 @@ int ret_compile(const uint8_t* tb, const uint64_t* to, uint64_t n, const uint32_
     for (uint64_t p = prev_lo; p <= prev_lo + prev_n; ++p) nodes[p].child_lo = end;
   }
   // 5. dictionary (open addressing, load <= 1/2), word offsets, arena
-  uint64_t dict_cap = 16;
-  while (dict_cap < 2 * dw.size()) dict_cap <<= 1;
+  const uint64_t dict_cap = dict_capacity(dw.size());
   uint64_t arena_bytes = 0;
   for (const WordRef& w : dw) arena_bytes += w.len;
   if (arena_bytes >= 0xFFFFFFFFull) {
@@ -236,20 +189,8 @@ int ret_compile(const uint8_t* tb, const uint64_t* to, uint64_t n, const uint32_
   uint8_t* base = r->blob.data();
   std::memcpy(base + o[0], nodes.data(), nodes.size() * sizeof(RetNode));
   std::memcpy(base + o[1], depth_ends.data(), depth_ends.size() * 4);
-  auto* dict = reinterpret_cast<DictSlot*>(base + o[2]);
-  auto* woff = reinterpret_cast<uint32_t*>(base + o[3]);
-  uint8_t* arena = base + o[4];
-  for (uint64_t s = 0; s < dict_cap; ++s) dict[s] = DictSlot{0, DICT_EMPTY_LEN, 0};
-  uint64_t ab = 0;
-  for (uint64_t w = 0; w < dw.size(); ++w) {
-    woff[w] = uint32_t(ab);
-    if (dw[w].len) std::memcpy(arena + ab, dw[w].p, dw[w].len);
-    ab += dw[w].len;
-    uint64_t s = dict_slot(dict_hash_host(dw[w].p, dw[w].len), dict_cap - 1);
-    while (dict[s].len != DICT_EMPTY_LEN) s = (s + 1) & (dict_cap - 1);
-    dict[s] = DictSlot{word_head_host(dw[w].p, dw[w].len), uint32_t(dw[w].len), uint32_t(w)};
-  }
-  woff[dw.size()] = uint32_t(ab);
+  dict_fill(dw.data(), dw.size(), reinterpret_cast<DictSlot*>(base + o[2]), dict_cap,
+            reinterpret_cast<uint32_t*>(base + o[3]), base + o[4]);
   auto* rid = reinterpret_cast<uint32_t*>(base + o[5]);
   auto* rex = reinterpret_cast<uint64_t*>(base + o[6]);
   bool any_expiry = false;
@@ -286,7 +227,7 @@ uint32_t ret_find_host(const emqx_gm_retained* r, const uint8_t* p, uint64_t len
   uint64_t s = 0;
   for (uint64_t e = 0; e <= len; ++e)
     if (e == len || p[e] == '/') {
-      const uint32_t w = host_word_find(v, p + s, e - s);
+      const uint32_t w = dict_find_host(v.words, p + s, e - s);
       if (w == NONE) return NONE;
       node = host_child(v, node, w);
       if (node == NONE) return NONE;
@@ -329,7 +270,7 @@ void ret_match_host(const emqx_gm_retained* r, const uint8_t* fb, const uint64_t
           if (e == len) hash = true;
           else ok = false;  // '#' before the last word: no stored word equals it
         } else {
-          const uint32_t w = host_word_find(v, p + s, wl);
+          const uint32_t w = dict_find_host(v.words, p + s, wl);
           if (w == NONE) ok = false;
           fw.push_back(w);
         }
@@ -370,30 +311,17 @@ void ret_match_host(const emqx_gm_retained* r, const uint8_t* fb, const uint64_t
 
 }  // namespace gm
 
-#define RET_GUARD_BEGIN try {
-#define RET_GUARD_END(ctx)                                               \
-  }                                                                      \
-  catch (const std::bad_alloc&) {                                        \
-    return gm::set_err((ctx), EMQX_GM_ENOMEM, "host allocation failed"); \
-  }                                                                      \
-  catch (const std::exception& e) {                                      \
-    return gm::set_err((ctx), EMQX_GM_EINVAL, e.what());                 \
-  }                                                                      \
-  catch (...) {                                                          \
-    return gm::set_err((ctx), EMQX_GM_EINVAL, "unknown error");          \
-  }
-
 extern "C" {
 
 int emqx_gm_retained_compile_host(const uint8_t* tb, const uint64_t* to, uint64_t n, const uint32_t* ids,
                                   const uint64_t* expiry, emqx_gm_retained** out) {
   if (!out) return EMQX_GM_EINVAL;
   *out = nullptr;
-  RET_GUARD_BEGIN
+  GM_GUARD_BEGIN
   std::string why;
   const int rc = gm::ret_compile(tb, to, n, ids, expiry, out, &why);
   return rc ? gm::set_err(nullptr, rc, "retained_build: " + why) : rc;
-  RET_GUARD_END(nullptr)
+  GM_GUARD_END(nullptr)
 }
 
 int emqx_gm_retained_build(emqx_gm_ctx* ctx, const uint8_t* tb, const uint64_t* to, uint64_t n, const uint32_t* ids,
@@ -401,7 +329,7 @@ int emqx_gm_retained_build(emqx_gm_ctx* ctx, const uint8_t* tb, const uint64_t* 
   if (!ctx || !out) return EMQX_GM_EINVAL;
   *out = nullptr;
   if (flags) return gm::set_err(ctx, EMQX_GM_EINVAL, "retained_build: flags");
-  RET_GUARD_BEGIN
+  GM_GUARD_BEGIN
   std::string why;
   emqx_gm_retained* r = nullptr;
   int rc = gm::ret_compile(tb, to, n, ids, expiry, &r, &why);
@@ -414,7 +342,7 @@ int emqx_gm_retained_build(emqx_gm_ctx* ctx, const uint8_t* tb, const uint64_t* 
   }
   *out = r;
   return EMQX_GM_OK;
-  RET_GUARD_END(ctx)
+  GM_GUARD_END(ctx)
 }
 
 int emqx_gm_retained_match(emqx_gm_ctx* ctx, const emqx_gm_retained* idx, const uint8_t* fb, const uint64_t* fo,
@@ -425,13 +353,13 @@ int emqx_gm_retained_match(emqx_gm_ctx* ctx, const emqx_gm_retained* idx, const 
   if (!idx->dev_base) return gm::set_err(ctx, EMQX_GM_EUNSUPPORTED, "retained_match: a host-only index");
   if (idx->device != ctx->device)
     return gm::set_err(ctx, EMQX_GM_EINVAL, "retained_match: the index is on another device");
-  RET_GUARD_BEGIN
+  GM_GUARD_BEGIN
   std::string why;
-  if (const int rc = gm::ret_check_batch(fb, fo, n, &why)) return gm::set_err(ctx, rc, "retained_match: " + why);
+  if (const int rc = gm::check_offsets(fb, fo, n, &why)) return gm::set_err(ctx, rc, "retained_match: " + why);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return gm::ret_match_device(ctx, const_cast<emqx_gm_retained*>(idx), fb, fo, n, now_ms,
                               (flags & EMQX_GM_RET_TIMED) != 0, out);
-  RET_GUARD_END(ctx)
+  GM_GUARD_END(ctx)
 }
 
 int emqx_gm_retained_expire(emqx_gm_ctx* ctx, emqx_gm_retained* idx, const uint8_t* tb, const uint64_t* to,
@@ -442,9 +370,9 @@ int emqx_gm_retained_expire(emqx_gm_ctx* ctx, emqx_gm_retained* idx, const uint8
   if (!idx->dev_base) return gm::set_err(ctx, EMQX_GM_EUNSUPPORTED, "retained_expire: a host-only index");
   if (idx->device != ctx->device)
     return gm::set_err(ctx, EMQX_GM_EINVAL, "retained_expire: the index is on another device");
-  RET_GUARD_BEGIN
+  GM_GUARD_BEGIN
   std::string why;
-  if (const int rc = gm::ret_check_batch(tb, to, n, &why)) return gm::set_err(ctx, rc, "retained_expire: " + why);
+  if (const int rc = gm::check_offsets(tb, to, n, &why)) return gm::set_err(ctx, rc, "retained_expire: " + why);
   if (!n) return EMQX_GM_OK;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   uint64_t found = 0;
@@ -458,7 +386,7 @@ int emqx_gm_retained_expire(emqx_gm_ctx* ctx, emqx_gm_retained* idx, const uint8
   idx->dv.flags |= gm::RET_HAS_EXPIRY;
   if (n_found) *n_found = found;
   return EMQX_GM_OK;
-  RET_GUARD_END(ctx)
+  GM_GUARD_END(ctx)
 }
 
 int emqx_gm_retained_info(const emqx_gm_retained* idx, emqx_gm_retained_info_t* info) {
@@ -478,34 +406,22 @@ int emqx_gm_retained_match_host(const emqx_gm_retained* idx, const uint8_t* fb, 
                                 uint64_t now_ms, emqx_gm_csr* out) {
   if (!idx || !out) return EMQX_GM_EINVAL;
   std::memset(out, 0, sizeof(*out));
-  RET_GUARD_BEGIN
+  GM_GUARD_BEGIN
   std::string why;
-  if (const int rc = gm::ret_check_batch(fb, fo, n, &why))
+  if (const int rc = gm::check_offsets(fb, fo, n, &why))
     return gm::set_err(nullptr, rc, "retained_match_host: " + why);
   std::vector<uint64_t> ro;
   std::vector<uint32_t> ids;
   gm::ret_match_host(idx, fb, fo, n, now_ms, ro, ids);
-  out->row_off = static_cast<uint64_t*>(malloc((n + 1) * 8));
-  out->ids = static_cast<uint32_t*>(malloc(std::max<size_t>(ids.size(), 1) * 4));
-  if (!out->row_off || !out->ids) {
-    emqx_gm_retained_csr_free_host(out);
-    return gm::set_err(nullptr, EMQX_GM_ENOMEM, "retained_match_host: result");
+  if (const int rc = gm::csr_to_malloc(ro, ids, out)) {
+    gm::csr_free_malloc(out);
+    return gm::set_err(nullptr, rc, "retained_match_host: result");
   }
-  std::memcpy(out->row_off, ro.data(), (n + 1) * 8);
-  if (!ids.empty()) std::memcpy(out->ids, ids.data(), ids.size() * 4);
-  out->n_rows = n;
-  out->nnz = ids.size();
   return EMQX_GM_OK;
-  RET_GUARD_END(nullptr)
+  GM_GUARD_END(nullptr)
 }
 
-int emqx_gm_retained_csr_free_host(emqx_gm_csr* csr) {
-  if (!csr) return EMQX_GM_EINVAL;
-  free(csr->row_off);
-  free(csr->ids);
-  std::memset(csr, 0, sizeof(*csr));
-  return EMQX_GM_OK;
-}
+int emqx_gm_retained_csr_free_host(emqx_gm_csr* csr) { return gm::csr_free_malloc(csr); }
 
 int emqx_gm_retained_last_times(const emqx_gm_retained* idx, double* ms3) {
   if (!idx || !ms3) return EMQX_GM_EINVAL;

@@ -42,12 +42,9 @@ struct alignas(16) RetNode {
 struct RetView {
   const RetNode* nodes;
   const uint32_t* depth_ends;  // [depth_max + 1]: topics of exactly that many words
-  const DictSlot* dict;        // word -> id; DictSlot::word holds the id, hash and layout as gm_common.h
-  const uint32_t* word_off;    // [n_words + 1] id -> byte offset in the arena (words in id order)
-  const uint8_t* arena;
+  DictView words;              // word -> id (gm_dict.h); DictSlot::word holds the id
   const uint32_t* ids;         // rank -> caller's id
   uint64_t* expiry;            // rank -> expiry in ms, 0 = never; mutated in place by expire
-  uint64_t dict_mask;
   uint32_t n_topics, n_nodes, n_words, depth_max;
   uint32_t flags;
 };
@@ -76,7 +73,6 @@ namespace gm {
 // gm_retained.cpp (host only)
 int ret_compile(const uint8_t* tb, const uint64_t* to, uint64_t n, const uint32_t* ids, const uint64_t* expiry,
                 emqx_gm_retained** out, std::string* why);
-int ret_check_batch(const uint8_t* b, const uint64_t* o, uint64_t n, std::string* why);
 void ret_match_host(const emqx_gm_retained* r, const uint8_t* fb, const uint64_t* fo, uint64_t n, uint64_t now,
                     std::vector<uint64_t>& row_off, std::vector<uint32_t>& ids);
 // the end node of a topic walked as an all-literal filter over the host tables (NONE: not stored)

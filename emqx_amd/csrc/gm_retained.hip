@@ -19,43 +19,11 @@
 
 #include <algorithm>
 
+#include "gm_device.h"
 #include "gm_retained.h"
 
 namespace gm {
 namespace {
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ uint32_t uni(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m, uint32_t lane) {
-  return __popcll(m & ((1ull << lane) - 1ull));
-}
-
-// id of the word p[0, len) in the index's dictionary, or NONE (hits verified by bytes)
-__device__ uint32_t ret_word_find(const RetView& v, const uint8_t* p, uint32_t len) {
-  uint32_t h = DICT_HASH_SEED;
-  uint64_t head = 0;
-  for (uint32_t i = 0; i < len; i += 8) {
-    uint64_t c = 0;
-    for (uint32_t k = 0; k < 8 && i + k < len; ++k) c |= uint64_t(p[i + k]) << (8 * k);
-    if (!i) head = c;
-    h = dict_hash_step(h, c);
-  }
-  h = dict_hash_final(h, len);
-  for (uint64_t s = dict_slot(h, v.dict_mask);; s = (s + 1) & v.dict_mask) {
-    const DictSlot e = v.dict[s];
-    if (e.len == DICT_EMPTY_LEN) return NONE;
-    if (e.len != len || e.head != head) continue;
-    if (len <= 8) return e.word;
-    const uint8_t* a = v.arena + v.word_off[e.word];
-    uint32_t k = 8;
-    while (k < len && a[k] == p[k]) ++k;
-    if (k == len) return e.word;
-  }
-}
 
 // the child of `parent` through word id w: binary search over its contiguous, ascending children
 __device__ uint32_t ret_child(const RetView& v, uint32_t parent, uint32_t w) {
@@ -162,7 +130,7 @@ __global__ __launch_bounds__(RET_WAVES_PER_BLOCK * 64) void k_ret_walk(RetView v
           uint32_t id;
           if (wl == 1 && p[s] == '+') id = RET_PLUS;
           else if (wl == 1 && p[s] == '#') id = NONE;  // '#' before the last word: no stored word equals it
-          else id = ret_word_find(v, p + s, wl);       // an unknown word ends the row empty
+          else id = dict_find<true>(v.words, p + s, wl);  // an unknown word ends the row empty
           wid[k] = id;
           bad |= id == NONE;
         }
@@ -303,7 +271,7 @@ __global__ __launch_bounds__(256) void k_ret_expire(RetView v, const uint8_t* __
     uint32_t node = 0, s = 0;
     for (uint32_t e = 0; e <= len && node != NONE; ++e)
       if (e == len || p[e] == '/') {
-        const uint32_t w = ret_word_find(v, p + s, e - s);
+        const uint32_t w = dict_find<true>(v.words, p + s, e - s);
         node = w == NONE ? NONE : ret_child(v, node, w);
         s = e + 1;
       }
@@ -319,38 +287,19 @@ __global__ __launch_bounds__(256) void k_ret_expire(RetView v, const uint8_t* __
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_found, (unsigned long long)__popcll(m));
 }
 
-struct Events {
-  hipEvent_t e[4] = {};
-  bool on = false;
-  ~Events() {
-    for (hipEvent_t x : e)
-      if (x) hipEventDestroy(x);
-  }
-};
-
 }  // namespace
 
 int ret_upload(emqx_gm_ctx* ctx, emqx_gm_retained* r) {
-  GM_HIP(ctx, hipSetDevice(ctx->device));
-  void* d = nullptr;
-  if (hipMalloc(&d, r->bytes) != hipSuccess) return set_err(ctx, EMQX_GM_ENOMEM, "retained_build: device tables");
-  hipError_t e = hipMemcpyAsync(d, r->blob.data(), r->bytes, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    hipFree(d);
-    return set_err(ctx, EMQX_GM_EDEVICE, std::string("retained_build: upload: ") + hipGetErrorString(e));
-  }
-  const uint8_t* hb = r->blob.data();
-  uint8_t* db = static_cast<uint8_t*>(d);
-  auto reb = [&](const void* p) { return db + (static_cast<const uint8_t*>(p) - hb); };
-  r->dv.nodes = reinterpret_cast<const RetNode*>(reb(r->hv.nodes));
-  r->dv.depth_ends = reinterpret_cast<const uint32_t*>(reb(r->hv.depth_ends));
-  r->dv.dict = reinterpret_cast<const DictSlot*>(reb(r->hv.dict));
-  r->dv.word_off = reinterpret_cast<const uint32_t*>(reb(r->hv.word_off));
-  r->dv.arena = reb(r->hv.arena);
-  r->dv.ids = reinterpret_cast<const uint32_t*>(reb(r->hv.ids));
-  r->dv.expiry = reinterpret_cast<uint64_t*>(reb(r->hv.expiry));
-  r->dev_base = d;
+  if (const int rc = table_upload(ctx, r->blob, r->bytes, "retained_build", &r->dev_base)) return rc;
+  const RetView& h = r->hv;
+  const void* hb = r->blob.data();
+  void* db = r->dev_base;
+  r->dv.nodes = rebase(h.nodes, hb, db);
+  r->dv.depth_ends = rebase(h.depth_ends, hb, db);
+  r->dv.words = DictView{rebase(h.words.dict, hb, db), rebase(h.words.word_off, hb, db), rebase(h.words.arena, hb, db),
+                         h.words.dict_mask};
+  r->dv.ids = rebase(h.ids, hb, db);
+  r->dv.expiry = rebase(h.expiry, hb, db);
   r->device = ctx->device;
   r->info.device_bytes = r->bytes;
   if (!r->info.lds_frames) {
@@ -363,8 +312,7 @@ int ret_upload(emqx_gm_ctx* ctx, emqx_gm_retained* r) {
 }
 
 void ret_free_device(emqx_gm_retained* r) {
-  hipSetDevice(r->device);
-  hipFree(r->dev_base);  // (waits for the device: no queued walk still reads the tables)
+  table_free(r->device, r->dev_base);  // (waits for the device: no queued walk still reads the tables)
   r->dev_base = nullptr;
 }
 
@@ -407,11 +355,9 @@ int ret_match_device(emqx_gm_ctx* ctx, emqx_gm_retained* r, const uint8_t* fb, c
   for (uint64_t i = 0; i <= n; ++i) off[i] = fo[i] - fo[0];
   if (nbytes - fo[0]) GM_HIP(ctx, hipMemcpyAsync(d_fb.p, fb + fo[0], nbytes - fo[0], hipMemcpyHostToDevice, st));
   GM_HIP(ctx, hipMemcpyAsync(d_fo.p, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-  Events ev;
-  if (timed) {
-    for (hipEvent_t& x : ev.e) GM_HIP(ctx, hipEventCreate(&x));
-    ev.on = true;
-  }
+  EventSet<4> ev;
+  if (timed)
+    if (const int rc = ev.create(ctx)) return rc;
   const size_t lds = gws ? 0 : size_t(wave_words) * 4 * RET_WAVES_PER_BLOCK;
   auto walk = [&](int fill, uint32_t* d_ids) {
     if (gws)

@@ -21,25 +21,6 @@ namespace gm {
 
 namespace {
 
-inline size_t al16(size_t x) { return (x + 15) & ~size_t(15); }
-
-int check_offsets(const uint8_t* b, const uint64_t* o, uint64_t n, std::string* why) {
-  if (n >= 0xFFFFFFFFull) {
-    *why = "more than 2^32 - 2 entries";
-    return EMQX_GM_EINVAL;
-  }
-  if (!o || (!b && n && o[n])) {
-    *why = "NULL buffer";
-    return EMQX_GM_EINVAL;
-  }
-  for (uint64_t i = 0; i < n; ++i)
-    if (o[i + 1] < o[i] || o[i + 1] - o[i] >= (1ull << 31)) {
-      *why = "offsets not ascending (or an entry of 2 GiB) at " + std::to_string(i);
-      return EMQX_GM_EINVAL;
-    }
-  return EMQX_GM_OK;
-}
-
 std::string slot_key(const uint8_t* p, uint64_t len, uint32_t group) {
   std::string k(reinterpret_cast<const char*>(&group), 4);
   if (len) k.append(reinterpret_cast<const char*>(p), len);
@@ -260,19 +241,6 @@ int sh_pick_host(emqx_gm_shared* sh, const emqx_gm_csr* m, uint32_t strategy, co
 
 }  // namespace gm
 
-#define SH_GUARD_BEGIN try {
-#define SH_GUARD_END(ctx)                                                \
-  }                                                                      \
-  catch (const std::bad_alloc&) {                                        \
-    return gm::set_err((ctx), EMQX_GM_ENOMEM, "host allocation failed"); \
-  }                                                                      \
-  catch (const std::exception& e) {                                      \
-    return gm::set_err((ctx), EMQX_GM_EINVAL, e.what());                 \
-  }                                                                      \
-  catch (...) {                                                          \
-    return gm::set_err((ctx), EMQX_GM_EINVAL, "unknown error");          \
-  }
-
 extern "C" {
 
 int emqx_gm_shared_compile_host(const uint8_t* ifb, const uint64_t* ifo, uint64_t n_index, const uint8_t* fb,
@@ -281,28 +249,21 @@ int emqx_gm_shared_compile_host(const uint8_t* ifb, const uint64_t* ifo, uint64_
                                 emqx_gm_shared** out) {
   if (!out) return EMQX_GM_EINVAL;
   *out = nullptr;
-  SH_GUARD_BEGIN
+  GM_GUARD_BEGIN
   std::string why;
   if (const int rc = gm::check_offsets(ifb, ifo, n_index, &why))
     return gm::set_err(nullptr, rc, "shared_compile_host: index filters: " + why);
   if (prev && prev->dev_base)
     return gm::set_err(nullptr, EMQX_GM_EUNSUPPORTED, "shared_compile_host: prev is a device table");
   // filter ids as emqx_gm_index_compile_host assigns them: the rank among the distinct filters
-  using Ref = std::pair<const uint8_t*, uint64_t>;
-  auto less = [](const Ref& a, const Ref& b) {
-    const uint64_t m = std::min(a.second, b.second);
-    const int c = m ? std::memcmp(a.first, b.first, m) : 0;
-    return c ? c < 0 : a.second < b.second;
-  };
-  std::vector<Ref> fs(n_index);
-  for (uint64_t i = 0; i < n_index; ++i) fs[i] = Ref{ifb + ifo[i], ifo[i + 1] - ifo[i]};
-  std::sort(fs.begin(), fs.end(), less);
-  fs.erase(std::unique(fs.begin(), fs.end(), [&](const Ref& a, const Ref& b) { return !less(a, b) && !less(b, a); }),
-           fs.end());
+  std::vector<gm::WordRef> fs(n_index);
+  for (uint64_t i = 0; i < n_index; ++i) fs[i] = gm::WordRef{ifb + ifo[i], ifo[i + 1] - ifo[i]};
+  std::sort(fs.begin(), fs.end(), gm::word_less);
+  fs.erase(std::unique(fs.begin(), fs.end(), gm::word_eq), fs.end());
   auto resolve = [&](const uint8_t* p, uint64_t len, uint32_t* id) {
-    const Ref key{p, len};
-    const auto it = std::lower_bound(fs.begin(), fs.end(), key, less);
-    if (it == fs.end() || less(key, *it)) return false;
+    const gm::WordRef key{p, len};
+    const auto it = std::lower_bound(fs.begin(), fs.end(), key, gm::word_less);
+    if (it == fs.end() || gm::word_less(key, *it)) return false;
     *id = uint32_t(it - fs.begin());
     return true;
   };
@@ -310,19 +271,7 @@ int emqx_gm_shared_compile_host(const uint8_t* ifb, const uint64_t* ifo, uint64_
   const int rc = gm::sh_compile(in, fs.size(), resolve, prev, prev ? prev->hv.rr : nullptr,
                                 prev ? prev->hv.st : nullptr, out, &why);
   return rc ? gm::set_err(nullptr, rc, "shared_compile_host: " + why) : rc;
-  SH_GUARD_END(nullptr)
-}
-
-static int sh_csr_host(const std::vector<uint64_t>& ro, const std::vector<uint32_t>& ids, emqx_gm_csr* out) {
-  const uint64_t n = ro.size() - 1;
-  out->row_off = static_cast<uint64_t*>(malloc((n + 1) * 8));
-  out->ids = static_cast<uint32_t*>(malloc(std::max<size_t>(ids.size(), 1) * 4));
-  if (!out->row_off || !out->ids) return EMQX_GM_ENOMEM;
-  std::memcpy(out->row_off, ro.data(), (n + 1) * 8);
-  if (!ids.empty()) std::memcpy(out->ids, ids.data(), ids.size() * 4);
-  out->n_rows = n;
-  out->nnz = ids.size();
-  return EMQX_GM_OK;
+  GM_GUARD_END(nullptr)
 }
 
 int emqx_gm_shared_pick_host(emqx_gm_shared* sh, const emqx_gm_csr* m, uint32_t strategy, const uint32_t* msg_hash,
@@ -336,7 +285,7 @@ int emqx_gm_shared_pick_host(emqx_gm_shared* sh, const emqx_gm_csr* m, uint32_t 
   if (strategy > EMQX_GM_SHARE_RANDOM) return gm::set_err(nullptr, EMQX_GM_EINVAL, "shared_pick_host: strategy");
   if (strategy == EMQX_GM_SHARE_HASH && !msg_hash && m->n_rows)
     return gm::set_err(nullptr, EMQX_GM_EINVAL, "shared_pick_host: msg_hash is required for EMQX_GM_SHARE_HASH");
-  SH_GUARD_BEGIN
+  GM_GUARD_BEGIN
   std::string why;
   if (const int rc = gm::sh_check_rows(sh, m, &why)) return gm::set_err(nullptr, rc, "shared_pick_host: " + why);
   std::lock_guard<std::mutex> lk(sh->mu);
@@ -344,24 +293,18 @@ int emqx_gm_shared_pick_host(emqx_gm_shared* sh, const emqx_gm_csr* m, uint32_t 
   std::vector<uint32_t> mem, slots;
   if (const int rc = gm::sh_pick_host(sh, m, strategy, msg_hash, seed, ro, mem, slots))
     return gm::set_err(nullptr, rc, "shared_pick_host: 2^32 - 1 hits or more");
-  int rc = sh_csr_host(ro, mem, out_members);
-  if (!rc) rc = sh_csr_host(ro, slots, out_slots);
+  int rc = gm::csr_to_malloc(ro, mem, out_members);
+  if (!rc) rc = gm::csr_to_malloc(ro, slots, out_slots);
   if (rc) {
-    emqx_gm_shared_csr_free_host(out_members);
-    emqx_gm_shared_csr_free_host(out_slots);
+    gm::csr_free_malloc(out_members);
+    gm::csr_free_malloc(out_slots);
     return gm::set_err(nullptr, rc, "shared_pick_host: result");
   }
   return EMQX_GM_OK;
-  SH_GUARD_END(nullptr)
+  GM_GUARD_END(nullptr)
 }
 
-int emqx_gm_shared_csr_free_host(emqx_gm_csr* csr) {
-  if (!csr) return EMQX_GM_EINVAL;
-  free(csr->row_off);
-  free(csr->ids);
-  std::memset(csr, 0, sizeof(*csr));
-  return EMQX_GM_OK;
-}
+int emqx_gm_shared_csr_free_host(emqx_gm_csr* csr) { return gm::csr_free_malloc(csr); }
 
 int emqx_gm_shared_slot(const emqx_gm_shared* sh, uint32_t slot, uint32_t* filter_id, uint32_t* group_id,
                         const uint32_t** members, uint64_t* n_members) {

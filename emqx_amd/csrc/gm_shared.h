@@ -40,21 +40,9 @@ namespace gm {
 
 constexpr uint32_t SH_UNSET = 0xFFFFFFFFu;
 
-#if defined(__HIPCC__)
-#define SH_HD __host__ __device__ __forceinline__
-#else
-#define SH_HD inline
-#endif
-SH_HD uint32_t sh_fmix(uint32_t h) {
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
-SH_HD uint32_t sh_mix(uint32_t a, uint32_t b) { return sh_fmix(sh_fmix(a + 0x9E3779B9u) + b); }
-SH_HD uint32_t sh_mix3(uint32_t a, uint32_t r, uint32_t s) { return sh_mix(sh_mix(a, r), s); }
+// (fmix is gm_common.h's fmix32)
+GM_HD uint32_t sh_mix(uint32_t a, uint32_t b) { return fmix32(fmix32(a + 0x9E3779B9u) + b); }
+GM_HD uint32_t sh_mix3(uint32_t a, uint32_t r, uint32_t s) { return sh_mix(sh_mix(a, r), s); }
 
 struct ShView {
   const uint32_t* sh_off;

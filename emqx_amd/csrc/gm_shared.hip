@@ -23,16 +23,11 @@
 
 #include <algorithm>
 
+#include "gm_device.h"
 #include "gm_shared.h"
 
 namespace gm {
 namespace {
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __global__ __launch_bounds__(256) void k_sh_count(ShView v, const uint32_t* __restrict__ ids, uint64_t nnz,
                                                   uint64_t* __restrict__ cnt) {
@@ -172,47 +167,29 @@ __global__ __launch_bounds__(64) void k_sh_rank(ShView v, const uint32_t* __rest
   }
 }
 
-struct Events {
-  hipEvent_t e[5] = {};
-  ~Events() {
-    for (hipEvent_t x : e)
-      if (x) hipEventDestroy(x);
-  }
-};
-
 inline uint32_t blocks_of(uint64_t n) { return uint32_t((n + 255) / 256); }
 
 }  // namespace
 
 int sh_upload(emqx_gm_ctx* ctx, emqx_gm_shared* sh) {
-  GM_HIP(ctx, hipSetDevice(ctx->device));
-  void* d = nullptr;
-  if (hipMalloc(&d, sh->bytes) != hipSuccess) return set_err(ctx, EMQX_GM_ENOMEM, "shared_build: device tables");
-  hipError_t e = hipMemcpyAsync(d, sh->blob.data(), sh->bytes, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    hipFree(d);
-    return set_err(ctx, EMQX_GM_EDEVICE, std::string("shared_build: upload: ") + hipGetErrorString(e));
-  }
-  const uint8_t* hb = sh->blob.data();
-  uint8_t* db = static_cast<uint8_t*>(d);
-  auto reb = [&](const void* p) { return reinterpret_cast<uint32_t*>(db + (static_cast<const uint8_t*>(p) - hb)); };
-  sh->dv.sh_off = reb(sh->hv.sh_off);
-  sh->dv.mem_off = reb(sh->hv.mem_off);
-  sh->dv.filter = reb(sh->hv.filter);
-  sh->dv.group = reb(sh->hv.group);
-  sh->dv.mem_ids = reb(sh->hv.mem_ids);
-  sh->dv.rr = reb(sh->hv.rr);
-  sh->dv.st = reb(sh->hv.st);
-  sh->dev_base = d;
+  if (const int rc = table_upload(ctx, sh->blob, sh->bytes, "shared_build", &sh->dev_base)) return rc;
+  const ShView& h = sh->hv;
+  const void* hb = sh->blob.data();
+  void* db = sh->dev_base;
+  sh->dv.sh_off = rebase(h.sh_off, hb, db);
+  sh->dv.mem_off = rebase(h.mem_off, hb, db);
+  sh->dv.filter = rebase(h.filter, hb, db);
+  sh->dv.group = rebase(h.group, hb, db);
+  sh->dv.mem_ids = rebase(h.mem_ids, hb, db);
+  sh->dv.rr = rebase(h.rr, hb, db);
+  sh->dv.st = rebase(h.st, hb, db);
   sh->device = ctx->device;
   sh->info.device_bytes = sh->bytes;
   return EMQX_GM_OK;
 }
 
 void sh_free_device(emqx_gm_shared* sh) {
-  hipSetDevice(sh->device);
-  hipFree(sh->dev_base);  // (waits for the device: no queued pick still reads the tables)
+  table_free(sh->device, sh->dev_base);  // (waits for the device: no queued pick still reads the tables)
   sh->dev_base = nullptr;
 }
 
@@ -298,8 +275,8 @@ int sh_pick_device(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, u
   PoolBuf d_cnt(ctx->pool, nnz * 8), d_hoff(ctx->pool, (nnz + 1) * 8), d_ro;
   if (!dev) d_ro = PoolBuf(ctx->pool, (n + 1) * 8);
   if (!d_cnt.p || !d_hoff.p || (!dev && !d_ro.p)) return set_err(ctx, EMQX_GM_ENOMEM, "shared_pick: device buffers");
-  Events ev;
-  for (hipEvent_t& x : ev.e) GM_HIP(ctx, hipEventCreate(&x));
+  EventSet<5> ev;
+  if (const int rc = ev.create(ctx)) return rc;
   GM_HIP(ctx, hipEventRecord(ev.e[0], st));
   // enumerate
   hipLaunchKernelGGL(k_sh_count, dim3(blocks_of(nnz)), dim3(256), 0, st, sh->dv, d_mids, nnz, d_cnt.as<uint64_t>());
@@ -388,19 +365,6 @@ int sh_pick_device(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, u
 
 }  // namespace gm
 
-#define SH_GUARD_BEGIN try {
-#define SH_GUARD_END(ctx)                                                \
-  }                                                                      \
-  catch (const std::bad_alloc&) {                                        \
-    return gm::set_err((ctx), EMQX_GM_ENOMEM, "host allocation failed"); \
-  }                                                                      \
-  catch (const std::exception& e) {                                      \
-    return gm::set_err((ctx), EMQX_GM_EINVAL, e.what());                 \
-  }                                                                      \
-  catch (...) {                                                          \
-    return gm::set_err((ctx), EMQX_GM_EINVAL, "unknown error");          \
-  }
-
 extern "C" {
 
 int emqx_gm_shared_build(emqx_gm_ctx* ctx, emqx_gm_index* idx, const uint8_t* fb, const uint64_t* fo,
@@ -419,7 +383,7 @@ int emqx_gm_shared_build(emqx_gm_ctx* ctx, emqx_gm_index* idx, const uint8_t* fb
     return gm::set_err(ctx, EMQX_GM_EINVAL, "shared_build: the index is on another device");
   if (prev && prev->dev_base && prev->device != ctx->device)
     return gm::set_err(ctx, EMQX_GM_EINVAL, "shared_build: prev is on another device");
-  SH_GUARD_BEGIN
+  GM_GUARD_BEGIN
   std::string why;
   // (prev is read, not modified; its lock -- taken before the context's, as a pick does -- keeps a
   // concurrent pick from queueing between the reads of its two state arrays)
@@ -449,7 +413,7 @@ int emqx_gm_shared_build(emqx_gm_ctx* ctx, emqx_gm_index* idx, const uint8_t* fb
   sh->idx = idx;
   *out = sh;
   return EMQX_GM_OK;
-  SH_GUARD_END(ctx)
+  GM_GUARD_END(ctx)
 }
 
 int emqx_gm_shared_pick_chunked(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, uint32_t strategy,
@@ -465,13 +429,13 @@ int emqx_gm_shared_pick_chunked(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx
   if (strategy == EMQX_GM_SHARE_HASH && !msg_hash && m->n_rows)
     return gm::set_err(ctx, EMQX_GM_EINVAL, "shared_pick: msg_hash is required for EMQX_GM_SHARE_HASH");
   if (n_chunks > gm::SH_RR_MAX_CHUNKS) return gm::set_err(ctx, EMQX_GM_EINVAL, "shared_pick: chunk count");
-  SH_GUARD_BEGIN
+  GM_GUARD_BEGIN
   std::string why;
   if (const int rc = gm::sh_check_rows(sh, m, &why)) return gm::set_err(ctx, rc, "shared_pick: " + why);
   std::lock_guard<std::mutex> tl(sh->mu);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return gm::sh_pick_device(ctx, sh, m, strategy, msg_hash, seed, n_chunks, out_members, out_slots);
-  SH_GUARD_END(ctx)
+  GM_GUARD_END(ctx)
 }
 
 int emqx_gm_shared_pick(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, uint32_t strategy,

@@ -81,6 +81,45 @@ def test_empty_index_and_empty_batch(ctx):
     assert _check(ctx, R.EDGE_TOPICS, []) == []
 
 
+# ------------------------------------------------------------------ the word lookup
+# words on both sides of the dictionary slot's 8-byte head, and words that share a whole head
+WORD_TOPICS = [b"w/" + b"k" * n for n in (0, 1, 7, 8, 9, 16, 17, 255)]
+WORD_TOPICS += [b"prefix00-tailA/x", b"prefix00-tailB/x", b"prefix00/x"]
+WORD_ABSENT = [b"w/" + b"k" * n for n in (2, 10, 254, 256)] + [b"prefix00-tailC/x", b"prefix00-tail/x"]
+WORD_FILTERS = WORD_TOPICS + WORD_ABSENT + [b"prefix00-tailA/+", b"+/x", b"w/#"]
+
+
+def test_word_lengths_and_equal_heads(ctx):
+    """The device word lookup (dict_find, gm_device.h) in k_ret_walk and
+    k_ret_expire: a literal filter finds its own topic and nothing else, a word
+    one byte shorter or longer or with another tail finds nothing."""
+    got = _check(ctx, WORD_TOPICS, WORD_FILTERS)
+    for i, t in enumerate(WORD_TOPICS):
+        assert got[i] == [i], t
+    assert got[len(WORD_TOPICS):len(WORD_TOPICS) + len(WORD_ABSENT)] == [[]] * len(WORD_ABSENT)
+    assert [len(r) for r in got[-3:]] == [1, 3, 8]
+    # expire: one expiry per listed topic, so a hit on the wrong topic would show
+    listed = WORD_TOPICS[::-1] + WORD_ABSENT
+    new = [1000 + k for k in range(len(listed))]
+    stored = [t for t in listed if t in WORD_TOPICS]
+    expiry = [dict(zip(listed, new))[t] for t in WORD_TOPICS]
+    ix = ctx.build_retained(WORD_TOPICS)
+    try:
+        assert ix.expire(listed, new) == len(stored) == len(WORD_TOPICS)
+        table = R.build_table(WORD_TOPICS, None, expiry)
+        for now in (999, 1000 + len(stored) // 2, max(new)):
+            want = R.match_rows(table, WORD_FILTERS, now)
+            assert _rows(ix.match(WORD_FILTERS, now)) == want, now
+            assert _rows(ix.match_host(WORD_FILTERS, now)) == want, now
+        dropped = {i for i, e in enumerate(expiry) if e <= 1000 + len(stored) // 2}
+        assert 0 < len(dropped) < len(stored)
+        assert _rows(ix.match([b"#"], 1000 + len(stored) // 2))[0] == sorted(
+            set(range(len(WORD_TOPICS))) - dropped, key=lambda i: WORD_TOPICS[i].split(b"/"))
+        assert _rows(ix.match(WORD_FILTERS, max(new))) == [[]] * len(WORD_FILTERS)
+    finally:
+        ix.release()
+
+
 # ------------------------------------------------------------------ chunk boundaries
 @pytest.mark.parametrize("k", [63, 64, 65, 129])
 def test_sibling_counts_around_the_wave(ctx, k):
