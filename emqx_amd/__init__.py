@@ -12,9 +12,11 @@ from .rules import TopicRuleIndex  # noqa: F401
 from .retainer import RetainedIndex, Retainer  # noqa: F401
 from .shared import SharedSub, SharedTable  # noqa: F401
 from .authz import Authz, AuthzTable  # noqa: F401
+from .cluster import ClusterRoutes, DestTable, ForwardPlan, build_dests  # noqa: F401
 from . import topic  # noqa: F401
 
 __all__ = ["Context", "Index", "DeviceCsr", "Trie", "Router", "SessionRouter", "Broker", "TopicRuleIndex", "topic",
            "RetainedIndex", "Retainer", "SharedTable", "SharedSub", "Authz", "AuthzTable",
+           "ClusterRoutes", "DestTable", "ForwardPlan", "build_dests",
            "GpuMatchError",
            "pack", "gen_filter_codes", "render_codes", "default_context"]

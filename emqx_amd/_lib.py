@@ -20,6 +20,9 @@ NO_TIMING = 0x4
 RET_TIMED = 0x1
 AUTHZ_TIMED = 0x1
 SHARE_HASH, SHARE_ROUND_ROBIN, SHARE_STICKY, SHARE_RANDOM = 0, 1, 2, 3
+DESTS_MAX_NODES = 4096
+DESTS_NO_SKIP = 0xFFFFFFFF
+DESTS_SKIP_UNKNOWN = 0x1
 OPEN_MIRROR_EAGER = 0x1
 OPEN_MIRROR_LAZY = 0x2
 IMAGE_NO_BLOB = 0x1
@@ -76,6 +79,18 @@ class RetainedInfo(C.Structure):
 class SharedInfo(C.Structure):
     _fields_ = [("n_slots", C.c_uint64), ("n_members", C.c_uint64), ("n_filters_with_slots", C.c_uint64),
                 ("device_bytes", C.c_uint64)]
+
+
+class DestsInfo(C.Structure):
+    _fields_ = [("n_routes", C.c_uint64), ("n_filters_with_routes", C.c_uint64), ("n_skipped_unknown", C.c_uint64),
+                ("device_bytes", C.c_uint64), ("n_nodes", C.c_uint32), ("reserved0", C.c_uint32)]
+
+
+class Forwards(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_pairs", C.c_uint64), ("node_off", C.POINTER(C.c_uint64)),
+                ("rows", C.POINTER(C.c_uint32)), ("filters", C.POINTER(C.c_uint32)),
+                ("row_routes", C.POINTER(C.c_uint32)), ("n_nodes", C.c_uint32), ("on_device", C.c_int32),
+                ("priv", C.c_void_p)]
 
 
 class AuthzDesc(C.Structure):
@@ -161,6 +176,11 @@ SIGNATURES = {
     "emqx_gm_shared_slot": (_i32, [_vp, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_vp), C.POINTER(_u64)]),
     "emqx_gm_shared_info": (_i32, [_vp, C.POINTER(SharedInfo)]),
     "emqx_gm_shared_release": (_i32, [_vp]),
+    "emqx_gm_dests_build": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, C.POINTER(_vp)]),
+    "emqx_gm_forward_plan": (_i32, [_vp, _vp, C.POINTER(Csr), _u32, C.POINTER(Forwards)]),
+    "emqx_gm_forwards_free": (_i32, [_vp, C.POINTER(Forwards)]),
+    "emqx_gm_dests_info": (_i32, [_vp, C.POINTER(DestsInfo)]),
+    "emqx_gm_dests_release": (_i32, [_vp]),
     "emqx_gm_authz_build": (_i32, [_vp, C.POINTER(AuthzDesc), _u32, C.POINTER(_vp)]),
     "emqx_gm_authz_check": (_i32, [_vp, _vp, C.POINTER(AuthzBatch), _u32, _vp, _vp]),
     "emqx_gm_authz_info": (_i32, [_vp, C.POINTER(AuthzInfo)]),
@@ -192,6 +212,11 @@ SIGNATURES = {
     "emqx_gm_shared_pick_chunked": (_i32, [_vp, _vp, C.POINTER(Csr), _u32, _vp, _u32, _u32, C.POINTER(Csr),
                                            C.POINTER(Csr)]),
     "emqx_gm_shared_last_times": (_i32, [_vp, C.POINTER(C.c_double)]),
+    "emqx_gm_dests_compile_host": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _u32, _u32, C.POINTER(_vp)]),
+    "emqx_gm_forward_plan_host": (_i32, [_vp, C.POINTER(Csr), _u32, C.POINTER(Forwards)]),
+    "emqx_gm_forwards_free_host": (_i32, [C.POINTER(Forwards)]),
+    "emqx_gm_forward_plan_chunked": (_i32, [_vp, _vp, C.POINTER(Csr), _u32, _u32, C.POINTER(Forwards)]),
+    "emqx_gm_dests_last_times": (_i32, [_vp, C.POINTER(C.c_double)]),
     "emqx_gm_authz_compile_host": (_i32, [C.POINTER(AuthzDesc), C.POINTER(_vp)]),
     "emqx_gm_authz_check_host": (_i32, [_vp, C.POINTER(AuthzBatch), _vp, _vp]),
     "emqx_gm_authz_last_kernel_ms": (_i32, [_vp, C.POINTER(C.c_double)]),

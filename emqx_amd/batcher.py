@@ -49,6 +49,15 @@ def _b(s) -> bytes:
     return s.encode() if isinstance(s, str) else bytes(s)
 
 
+class _Sent:
+    """A remote node route whose forward already left with its window's
+    forward_batch: the node and the recorded result."""
+    __slots__ = ("node", "res")
+
+    def __init__(self, node, res):
+        self.node, self.res = node, res
+
+
 def is_sys(topic: bytes) -> bool:
     """emqx_message:is_sys/1: a $SYS/ topic (not counted in the publish/drop metrics)."""
     return topic.startswith(b"$SYS/")
@@ -60,8 +69,9 @@ class GpuRoutes:
     nif/emqx_gpu_match_batcher.erl).  A filter is in the index while it has a
     local subscriber or another destination (route_add)."""
 
-    def __init__(self, ctx, node: bytes = b"node"):
+    def __init__(self, ctx, node: bytes = b"node", cluster=None):
         self.ctx, self.node = ctx, _b(node)
+        self.cluster = cluster                 # a ClusterRoutes: the node destinations, for the window's forward plan
         self.index = ctx.build_index([], subs=[])  # load_index([], []) at init
         self.ops: List[Tuple[bytes, int, str]] = []  # since the snapshot, oldest first
         self.ids: Dict[object, int] = {}       # subscriber -> id
@@ -123,6 +133,9 @@ class GpuRoutes:
                 self.other[f] = new
             else:
                 self.other.pop(f, None)
+            if self.cluster is not None and not isinstance(dest, tuple):
+                # the node destination itself, in the critical section that queues the mark
+                (self.cluster.add_route if d > 0 else self.cluster.delete_route)(f, dest)
             if old == 0 and new > 0:
                 self.ops.append((f, 0, "route_add"))
             elif old > 0 and new == 0:
@@ -204,7 +217,17 @@ class PublishBatcher:
     The picked member gets ``deliver(sub, filter, msg)``; if that fails the
     caller walks the rest of subscribers/2, as dispatch/4's FailedSubs loop
     does.  A group the table holds no member for goes to ``shared_dispatch``.
-    Without ``shared`` nothing changes."""
+    Without ``shared`` nothing changes.
+
+    ``cluster`` (a ClusterRoutes; needs ``routes``): a window's remote node
+    routes come from ONE ``cluster.plan`` over the window's matched rows and
+    go out with ONE ``forward_batch(node, [(filter, msg), ...])`` per node with
+    work -- the node's pairs in publish order -- instead of lookup_routes/1 and
+    ``forward`` per (message, route).  What ``forward_batch`` returns (an
+    exception: ("error", "badrpc")) is recorded as the result of each of its
+    pairs.  ``lookup_routes`` is then consulted for group destinations only.
+    A message's forwards leave with its window, so ``submit`` takes the
+    message too.  Without ``cluster`` nothing changes."""
 
     def __init__(self, groups_fn: Optional[Callable[[Sequence[bytes]], List[Row]]] = None, max_batch: int = 4096,
                  window_s: float = 0.001, subscribers: Optional[Dict[int, object]] = None,
@@ -218,7 +241,8 @@ class PublishBatcher:
                  on_dropped: Optional[Callable[[object], None]] = None,
                  persist: Optional[Callable[[bytes, object], None]] = None,
                  routes: Optional[GpuRoutes] = None, shared=None, shared_strategy: str = "round_robin",
-                 shared_hash: Optional[Callable[[bytes, object], int]] = None):
+                 shared_hash: Optional[Callable[[bytes, object], int]] = None, cluster=None,
+                 forward_batch: Optional[Callable[[bytes, List[Tuple[bytes, object]]], object]] = None):
         if routes is None and isinstance(getattr(groups_fn, "__self__", None), GpuRoutes):
             routes = groups_fn.__self__
         if groups_fn is None:
@@ -232,7 +256,11 @@ class PublishBatcher:
                 subscribers = routes.subs
         if shared is not None and routes is None:
             raise TypeError("PublishBatcher(shared=...) needs routes (the window's matched rows)")
+        if cluster is not None and routes is None:
+            raise TypeError("PublishBatcher(cluster=...) needs routes (the window's matched rows)")
         self.routes, self.shared, self.shared_strategy = routes, shared, shared_strategy
+        self.cluster = cluster
+        self.forward_batch = forward_batch or (lambda node, pairs: ("error", "badrpc"))
         self.shared_hash = shared_hash or (lambda topic, msg: zlib.crc32(topic))
         self.groups_fn = groups_fn
         self.max_batch = max_batch
@@ -253,7 +281,7 @@ class PublishBatcher:
         self.batches = 0
         self.messages = 0
         self._mlock = threading.Lock()
-        self._pending: List[Tuple[bytes, Future]] = []
+        self._pending: List[Tuple[bytes, Future, object]] = []
         self._deadline: Optional[float] = None
         self._cv = threading.Condition()
         self._closed = False
@@ -263,14 +291,14 @@ class PublishBatcher:
             self._thread.start()
 
     # ---------------------------------------------------------------- server side
-    def submit(self, topic) -> Future:
+    def submit(self, topic, msg=None) -> Future:
         """Queue one topic's match; the future resolves to ("ok", row) or
         ("error", reason) once its batch is matched (at most window_s after the
         batch's first topic)."""
         fut: Future = Future()
         flush = None
         with self._cv:
-            self._pending.append((_b(topic), fut))
+            self._pending.append((_b(topic), fut, msg))
             if len(self._pending) == 1:
                 self._deadline = self.clock() + self.window_s  # the window starts with the batch
                 self._cv.notify()
@@ -323,24 +351,53 @@ class PublishBatcher:
 
     def _rows(self, topics: Sequence[bytes], msgs: Optional[Sequence[object]] = None):
         try:
-            if self.shared is not None:  # the window's shared picks: one device call
+            if self.shared is not None or self.cluster is not None:
                 rows, idx, csr = self.routes.groups_rows(list(topics))
-                hashes = None
-                if self.shared_strategy.startswith("hash"):
-                    msgs = msgs if msgs is not None else [None] * len(topics)
-                    hashes = [self.shared_hash(t, m) & 0xFFFFFFFF for t, m in zip(topics, msgs)]
-                picks = self.shared.dispatch_batch(idx, csr, self.shared_strategy, hashes)
-                return [("ok", r, p) for r, p in zip(rows, picks)]
+                msgs = msgs if msgs is not None else [None] * len(topics)
+                picks = [None] * len(rows)
+                if self.shared is not None:  # the window's shared picks: one device call
+                    hashes = None
+                    if self.shared_strategy.startswith("hash"):
+                        hashes = [self.shared_hash(t, m) & 0xFFFFFFFF for t, m in zip(topics, msgs)]
+                    picks = self.shared.dispatch_batch(idx, csr, self.shared_strategy, hashes)
+                if self.cluster is None:
+                    return [("ok", r, p) for r, p in zip(rows, picks)]
+                return [("ok", r, p, w) for r, p, w in zip(rows, picks, self._forward_window(idx, csr, msgs))]
             return [("ok", r) for r in self.groups_fn(list(topics))]
         except Exception as e:  # the NIF's {error, _}: every caller takes the reference path
             return [("error", str(e))] * len(topics)
 
+    def _forward_window(self, idx, csr, msgs):
+        """The window's remote node routes: one plan call, one forward_batch per
+        node with work.  Per row, [(node, filter, result)]."""
+        plan = self.cluster.plan(idx, csr)
+        names: Dict[int, bytes] = {}
+        out: List[list] = [[] for _ in msgs]
+        for k in range(len(plan.node_off) - 1):
+            rws, fls = plan.node(k)
+            if not len(rws):
+                continue
+            node = self.cluster.nodes[k]
+            pairs = []
+            for r, f in zip(rws.tolist(), fls.tolist()):
+                name = names.get(f)
+                if name is None:
+                    name = names[f] = idx.filter(f)
+                pairs.append((r, name))
+            try:
+                res = self.forward_batch(node, [(name, msgs[r]) for r, name in pairs])
+            except Exception:
+                res = ("error", "badrpc")
+            for r, name in pairs:
+                out[r].append((node, name, res))
+        return out
+
     def _match(self, batch):
-        rows = self._rows([t for t, _ in batch])
+        rows = self._rows([t for t, _, _ in batch], [m for _, _, m in batch])
         with self._mlock:
             self.batches += 1
             self.messages += len(batch)
-        for (_, fut), row in zip(batch, rows):
+        for (_, fut, _), row in zip(batch, rows):
             fut.set_result(row)
 
     # ---------------------------------------------------------------- caller side
@@ -361,7 +418,7 @@ class PublishBatcher:
         """emqx_broker:publish/1 with the match batched: blocks until the batch
         holding the topic is matched, then routes in the calling thread."""
         t = self.prepare(topic, msg)
-        return self.route_row(self.submit(t).result(), t, msg)
+        return self.route_row(self.submit(t, msg).result(), t, msg)
 
     def publish_batch(self, items: Sequence[Tuple[object, object]]) -> List[Result]:
         """Messages the caller already holds: one groups call, results in order."""
@@ -376,11 +433,14 @@ class PublishBatcher:
         """route(aggre(Routes)) over a matched row (emqx_broker.erl:245-273)."""
         if row[0] == "ok":
             routes: List[tuple] = [(f, self.node, ids) for f, ids in row[1] if len(ids)]
+            sent = row[3] if len(row) > 3 else None  # the window's forwards of this row: [(node, filter, result)]
             other = [(f, d) for f, _ in row[1] if f in self.others for d in self.lookup_routes(f)
-                     if isinstance(d, tuple) or _b(d) != self.node]
+                     if isinstance(d, tuple) or (sent is None and _b(d) != self.node)]
+            if sent is not None:
+                other += [(f, _Sent(node, res)) for node, f, res in sent]
         else:  # the reference path
             routes, other = [], list(self.fallback(topic)) if self.fallback else []
-        picks = {(_b(g), f): sub for g, f, sub in row[2]} if len(row) > 2 else None
+        picks = {(_b(g), f): sub for g, f, sub in row[2]} if len(row) > 2 and row[2] is not None else None
         routes += self.aggre(other)
         if not routes:  # route([], _): no subscribers anywhere
             self.dropped(topic, msg)
@@ -393,7 +453,7 @@ class PublishBatcher:
     @staticmethod
     def aggre(routes: Sequence[Tuple[bytes, object]]) -> List[tuple]:
         """aggre/1: (filter, node) per node route, one (filter, group) per shared group."""
-        nodes = [(f, _b(d)) for f, d in routes if not isinstance(d, tuple)]
+        nodes = [(f, d if isinstance(d, _Sent) else _b(d)) for f, d in routes if not isinstance(d, tuple)]
         groups = sorted({(f, ("group", d[0])) for f, d in routes if isinstance(d, tuple)})
         return nodes + groups
 
@@ -402,6 +462,8 @@ class PublishBatcher:
             f, node, ids = r
             return (node, f, self.dispatch_ids(f, ids, topic, msg))
         f, d = r
+        if isinstance(d, _Sent):  # forwarded with its window's batch: the recorded result
+            return (d.node, f, d.res)
         if isinstance(d, tuple):  # ("group", G): emqx_shared_sub:dispatch/3
             if picks is not None and (_b(d[1]), f) in picks:
                 return ("share", f, self.deliver_shared(d[1], f, picks[(_b(d[1]), f)], msg))

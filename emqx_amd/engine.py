@@ -382,6 +382,12 @@ class Context:
         from .shared import build_shared
         return build_shared(self, index, slots, prev)
 
+    def build_dests(self, index: Index, routes, n_nodes: int, skip_unknown: bool = False):
+        """A route-destination table bound to ``index`` (emqx_gm_dests_build):
+        ``routes`` is [(filter, node id)], see :mod:`emqx_amd.cluster`."""
+        from .cluster import build_dests
+        return build_dests(self, index, routes, n_nodes, skip_unknown)
+
     def build_authz(self, table):
         """An authorization table (emqx_gm_authz_build) from an ``AuthzTable``:
         the chain of file and built-in-database sources compiled into HBM, see

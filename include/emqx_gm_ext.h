@@ -163,6 +163,28 @@ int emqx_gm_shared_pick_chunked(emqx_gm_ctx *ctx, emqx_gm_shared *sh, const emqx
                                 emqx_gm_csr *out_members, emqx_gm_csr *out_slots);
 int emqx_gm_shared_last_times(const emqx_gm_shared *sh, double *ms4);
 
+/* Test and measurement support for the route-destination table (no product
+ * path uses these).  compile_host: the table compiled on the host alone against
+ * the filter set index_filter_* as emqx_gm_index_compile_host compiles it (ids
+ * = ranks among the distinct filters; no device, no context);
+ * emqx_gm_forward_plan refuses the result.  plan_host: the single-threaded walk
+ * of emqx_gm_forward_plan over the table's host copy (host rows; any table);
+ * the arrays are malloc'd (free with emqx_gm_forwards_free, or, in a build
+ * without the device half, emqx_gm_forwards_free_host).  plan_chunked:
+ * emqx_gm_forward_plan with the partition's chunk count forced (0: the
+ * library's rule, at most 1024).  last_times: device ms of the last plan's
+ * enumerate, expand and partition passes, and of the whole call on the stream. */
+int emqx_gm_dests_compile_host(const uint8_t *index_filter_bytes, const uint64_t *index_filter_off,
+                               uint64_t n_index_filters, const uint8_t *filter_bytes, const uint64_t *filter_off,
+                               const uint32_t *node_ids, uint64_t n_routes, uint32_t n_nodes, uint32_t flags,
+                               emqx_gm_dests **out);
+int emqx_gm_forward_plan_host(const emqx_gm_dests *dt, const emqx_gm_csr *matches, uint32_t skip_node,
+                              emqx_gm_forwards *out);
+int emqx_gm_forwards_free_host(emqx_gm_forwards *fw);
+int emqx_gm_forward_plan_chunked(emqx_gm_ctx *ctx, emqx_gm_dests *dt, const emqx_gm_csr *matches,
+                                 uint32_t skip_node, uint32_t n_chunks, emqx_gm_forwards *out);
+int emqx_gm_dests_last_times(const emqx_gm_dests *dt, double *ms4);
+
 /* Test and measurement support for the authorization table (no product path
  * uses these).  compile_host: the table compiled on the host alone (no device,
  * no context); emqx_gm_authz_check refuses it.  check_host: the walk of

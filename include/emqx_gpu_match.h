@@ -269,7 +269,8 @@ int emqx_gm_index_update(emqx_gm_ctx *ctx, emqx_gm_index *prev, const uint8_t *f
  * another destination (a remote node or a shared group: do_add_route/2 with
  * a dest other than the local node): a filter is in the index while it has a
  * local subscriber OR that mark, so its matches still come back (with an
- * empty subscriber segment) for the caller's lookup_routes/1.  In a built
+ * empty subscriber segment) for the caller's lookup_routes/1 -- or, for node
+ * destinations, for emqx_gm_forward_plan below.  In a built
  * index, a filter given no subscribers carries the mark.
  * Returns a NEW snapshot (RCU, as emqx_gm_index_update): route changes are
  * patched into a device copy of the newest snapshot's tables and the new
@@ -608,6 +609,97 @@ int emqx_gm_shared_slot(const emqx_gm_shared *sh, uint32_t slot, uint32_t *filte
 int emqx_gm_shared_info(const emqx_gm_shared *sh, emqx_gm_shared_info_t *info);
 /* drops the table and its reference on the snapshot */
 int emqx_gm_shared_release(emqx_gm_shared *sh);
+
+/* ---- cluster forwards (gm_dests.cpp / gm_dests.hip): a window's remote routes, one list per node ----
+ * A filter whose destination is another node comes back from a match as a route
+ * mark only; the reference then reads the emqx_route bag per matched filter
+ * (lookup_routes/1, apps/emqx/src/emqx_router.erl:136) and calls forward/3 once
+ * per (message, route) (route/2, do_route/2, aggre/1, apps/emqx/src/
+ * emqx_broker.erl:214, 245-293).  Here the NODE destinations of emqx_route live
+ * in HBM and one call turns a publish window's matched rows into one forward
+ * list per node, so the caller sends one RPC per node per window.  Group
+ * destinations ({Group, Node}) stay with the shared-subscription table, whose
+ * slots are aggre/1's deduplicated {To, Group} entries.
+ * TABLE: a set of (filter, node) routes bound to ONE plain snapshot; node is a
+ * caller-assigned dense id < n_nodes, 1 <= n_nodes <= EMQX_GM_DESTS_MAX_NODES
+ * (the cap bounds the per-chunk histogram of the partition: one workgroup keeps
+ * a whole node histogram in 16 KiB of LDS).  A pair given twice is stored once
+ * (do_add_route/2 checks lists:member, emqx_router.erl:112-116); a filter's
+ * nodes are stored ascending.  The table is immutable: a changed route set or a
+ * new snapshot (filter ids shift) means a new build.
+ * HIT: a (window row, matched filter id, node of that filter) triple with
+ * node != skip_node.  The caller passes its own node id as skip_node (the local
+ * dispatch is the fan-out's job); EMQX_GM_DESTS_NO_SKIP skips nothing.
+ * BATCH ORDER: rows ascending, then filter ids in the order the row holds them,
+ * then nodes ascending.
+ * RESULT (emqx_gm_forwards): node k's forwards are the entries [node_off[k],
+ * node_off[k + 1]) of rows / filters, IN BATCH ORDER: emqx_rpc keys its channel
+ * by topic, so the forwards of one filter to one node must arrive in publish
+ * order (a stable partition keeps it; an arrival-order ticket would not).
+ * row_routes[r] is the number of {To, Node} routes of row r, skip_node's
+ * included (saturating at 2^32 - 1): a row with 0 here and no shared slot is
+ * route([], _), the dropped / no_subscribers case (emqx_broker.erl:245-248).
+ * EQUIVALENCE: run, per message in window order, match_routes/1 over the row
+ * (emqx_router.erl:128-134), lookup_routes/1 over the bag, aggre/1 clause by
+ * clause (its lists:usort on meeting a group route included: node entries are
+ * distinct terms and never equal a group entry, so every one survives it) and
+ * route/2 with node() = skip_node, recording every forward(Node, To, Delivery):
+ * per node, the recorded (row, To) sequence equals the plan's list -- rows in
+ * window order; within one row as a set (the reference's order inside one
+ * message follows the trie's match order). */
+typedef struct emqx_gm_dests emqx_gm_dests;
+#define EMQX_GM_DESTS_MAX_NODES 4096u
+#define EMQX_GM_DESTS_NO_SKIP 0xFFFFFFFFu
+#define EMQX_GM_DESTS_SKIP_UNKNOWN 0x1u /* build flag: drop (and count) routes of filters not in the snapshot */
+typedef struct {
+  uint64_t n_routes;              /* distinct (filter, node) pairs stored                          */
+  uint64_t n_filters_with_routes; /* distinct filters that carry a route                           */
+  uint64_t n_skipped_unknown;     /* input routes dropped under EMQX_GM_DESTS_SKIP_UNKNOWN          */
+  uint64_t device_bytes;          /* resident table bytes in HBM (0: host-only table)              */
+  uint32_t n_nodes;
+  uint32_t reserved0;
+} emqx_gm_dests_info_t;
+typedef struct {
+  uint64_t n_rows;      /* rows of the window                                     */
+  uint64_t n_pairs;     /* hits = entries of rows / filters (< 2^32 - 1)          */
+  uint64_t *node_off;   /* [n_nodes + 1]                                          */
+  uint32_t *rows;       /* [n_pairs] window row of each forward                   */
+  uint32_t *filters;    /* [n_pairs] its filter id (the forward's To)             */
+  uint32_t *row_routes; /* [n_rows] node routes of the row, skip_node's included  */
+  uint32_t n_nodes;
+  int32_t on_device;    /* the arrays are device pointers                         */
+  void *priv;           /* the owning context (NULL: malloc'ed by the host walk)  */
+} emqx_gm_forwards;
+/* The node routes of emqx_route bound to ONE plain snapshot `idx`, which the
+ * table retains.  Route i is filter filter_bytes[filter_off[i] ..
+ * filter_off[i+1]) -> node_ids[i].  A filter that is not in the snapshot:
+ * EMQX_GM_EINVAL with the filter named in emqx_gm_last_error, or, with
+ * EMQX_GM_DESTS_SKIP_UNKNOWN, dropped and counted.  node_ids[i] >= n_nodes,
+ * n_nodes outside [1, EMQX_GM_DESTS_MAX_NODES], an unknown flag and bad
+ * offsets (checked as emqx_gm_retained_build checks them): EMQX_GM_EINVAL
+ * before any device work.  Sharded, shard and overlay snapshots:
+ * EMQX_GM_EUNSUPPORTED.  On a multi-device context the table lives on the
+ * first listed device. */
+int emqx_gm_dests_build(emqx_gm_ctx *ctx, emqx_gm_index *idx, const uint8_t *filter_bytes,
+                        const uint64_t *filter_off, const uint32_t *node_ids, uint64_t n_routes,
+                        uint32_t n_nodes, uint32_t flags, emqx_gm_dests **out);
+/* The forward plan of `matches`, rows of the bound snapshot as emqx_gm_match
+ * returns them: a host CSR, or a device CSR (on_device).  The result comes
+ * back on the same side (free it with emqx_gm_forwards_free).  Host rows are
+ * checked before any device work (n_rows < 2^32 - 1, row_off from 0 to nnz
+ * ascending, every id < n_filters: else EMQX_GM_EINVAL); for device rows the
+ * kernels skip an id >= n_filters and clamp an offset past nnz.  skip_node >=
+ * n_nodes other than EMQX_GM_DESTS_NO_SKIP skips nothing either.  2^32 - 1
+ * hits or more in one call: EMQX_GM_EOVERFLOW, detected after the counting
+ * pass, before any output is sized; nothing is returned.  The result does not
+ * depend on how the library cuts the hits into chunks. */
+int emqx_gm_forward_plan(emqx_gm_ctx *ctx, emqx_gm_dests *dt, const emqx_gm_csr *matches, uint32_t skip_node,
+                         emqx_gm_forwards *out);
+/* frees a plan (ctx may be NULL for a result of emqx_gm_forward_plan_host) */
+int emqx_gm_forwards_free(emqx_gm_ctx *ctx, emqx_gm_forwards *fw);
+int emqx_gm_dests_info(const emqx_gm_dests *dt, emqx_gm_dests_info_t *info);
+/* drops the table and its reference on the snapshot */
+int emqx_gm_dests_release(emqx_gm_dests *dt);
 
 /* ---- authorization check (gm_authz.cpp / gm_authz.hip): the first matching ACL rule per request ----
  * Every PUBLISH and SUBSCRIBE passes emqx_authz:authorize/5 before the router;
