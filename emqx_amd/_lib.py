@@ -51,6 +51,19 @@ class Csr(C.Structure):
                 ("priv", C.c_void_p)]
 
 
+class Window(C.Structure):
+    _fields_ = [("topic_bytes", C.c_void_p), ("topic_off", C.c_void_p), ("n_topics", C.c_uint64)]
+
+
+class CombinerOpts(C.Structure):
+    _fields_ = [("max_windows", C.c_uint32), ("max_topics", C.c_uint64), ("max_in_flight", C.c_uint32),
+                ("min_windows", C.c_uint32), ("linger_us", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
+class CombinerStats(C.Structure):
+    _fields_ = [("windows", C.c_uint64), ("groups", C.c_uint64), ("max_group", C.c_uint64), ("solo", C.c_uint64)]
+
+
 class IndexInfo(C.Structure):
     _fields_ = [("n_filters", C.c_uint64), ("n_wildcard", C.c_uint64), ("n_nodes", C.c_uint64),
                 ("n_edges", C.c_uint64), ("n_words", C.c_uint64), ("n_subs", C.c_uint64),
@@ -151,6 +164,11 @@ SIGNATURES = {
     "emqx_gm_devices": (_i32, [_vp, _vp, C.POINTER(_u32)]),
     "emqx_gm_fanout": (_i32, [_vp, _vp, C.POINTER(Csr), _u32, C.POINTER(Csr)]),
     "emqx_gm_match_fanout": (_i32, [_vp, _vp, _vp, _vp, _u64, _u32, C.POINTER(Csr), C.POINTER(Csr)]),
+    "emqx_gm_match_windows": (_i32, [_vp, _vp, C.POINTER(Window), _u32, _u32, C.POINTER(Csr), C.POINTER(Csr)]),
+    "emqx_gm_combiner_open": (_i32, [_vp, C.POINTER(CombinerOpts), C.POINTER(_vp)]),
+    "emqx_gm_combiner_match": (_i32, [_vp, _vp, _vp, _vp, _u64, _u32, C.POINTER(Csr), C.POINTER(Csr)]),
+    "emqx_gm_combiner_stats": (_i32, [_vp, C.POINTER(CombinerStats)]),
+    "emqx_gm_combiner_close": (_i32, [_vp]),
     "emqx_gm_csr_free": (_i32, [_vp, C.POINTER(Csr)]),
     "emqx_gm_last_stats": (_i32, [_vp, C.POINTER(MatchStats)]),
     "emqx_gm_filter_ranks": (_i32, [_vp, _vp, _u64, _vp, C.POINTER(_u64)]),

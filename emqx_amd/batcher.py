@@ -69,9 +69,10 @@ class GpuRoutes:
     nif/emqx_gpu_match_batcher.erl).  A filter is in the index while it has a
     local subscriber or another destination (route_add)."""
 
-    def __init__(self, ctx, node: bytes = b"node", cluster=None):
+    def __init__(self, ctx, node: bytes = b"node", cluster=None, combiner=None):
         self.ctx, self.node = ctx, _b(node)
         self.cluster = cluster                 # a ClusterRoutes: the node destinations, for the window's forward plan
+        self.combiner = combiner               # a Combiner of ctx (load-info coalesce): the batch call goes through it
         self.index = ctx.build_index([], subs=[])  # load_index([], []) at init
         self.ops: List[Tuple[bytes, int, str]] = []  # since the snapshot, oldest first
         self.ids: Dict[object, int] = {}       # subscriber -> id
@@ -172,7 +173,8 @@ class GpuRoutes:
             raise RuntimeError("stale_index")
         idx = self.index
         # (the NIF's fanout_batch/2: emqx_gm_match_fanout, the match and its fan-out in one call)
-        (ro, ids), (fro, fids) = self.ctx.match_fanout(idx, list(topics), exact=True)
+        # (with a combiner: the same call, coalesced with the windows of concurrent callers)
+        (ro, ids), (fro, fids) = (self.combiner or self.ctx).match_fanout(idx, list(topics), exact=True)
         out = []
         for k in range(len(ro) - 1):
             row, pos = [], int(fro[k])

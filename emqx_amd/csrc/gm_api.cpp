@@ -6,9 +6,12 @@
 #include <cstring>
 #include <new>
 #include <stdexcept>
+#include <string>
+#include <vector>
 
 #include <sys/mman.h>
 
+#include "gm_combine.h"
 #include "gm_internal.h"
 #include "../../include/emqx_gm_ext.h"
 
@@ -392,6 +395,7 @@ int emqx_gm_host_free(emqx_gm_ctx* ctx, void* p) {
 
 int emqx_gm_close(emqx_gm_ctx* ctx) {
   if (!ctx) return EMQX_GM_EINVAL;
+  gm::free_combiners(ctx);  // (closed first: no group is on the device past here)
   for (emqx_gm_ctx* m : ctx->members) emqx_gm_close(m);
   ctx->members.clear();
   {
@@ -808,6 +812,260 @@ int emqx_gm_match_fanout(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8
   if (rc != EMQX_GM_OK) emqx_gm_csr_free(ctx, matches);  // (the error message stays the fan-out's)
   return rc;
 }
+
+// ---- publish windows coalesced into one device round trip (emqx_gm_match_windows,
+// emqx_gm_combiner): every scheduler of a node publishes at once
+// (apps/emqx/src/emqx_broker.erl:204-215, 296-322, emqx_trie.erl:66-70), each
+// with a window too small to fill the device; a group of them runs as one
+// batch (gm_host.cpp run_host_windows, gm_windows.hip k_rows_split) ----
+namespace {
+constexpr uint32_t kGroupWindows = 64, kGroupWindowsMax = 256;
+
+// 0: offsets not monotone; 1: the window runs alone through the ordinary call
+// (not a small call, a topic past 65,535 B, more than the mapped text limit); 2: it may join a group
+int window_kind(const emqx_gm_index* idx, const emqx_gm_window& w, uint32_t flags, bool fan) {
+  uint64_t lng = 0;
+  for (uint64_t i = 0; i < w.n_topics; ++i) {
+    if (w.topic_off[i + 1] < w.topic_off[i]) return 0;
+    lng |= (w.topic_off[i + 1] - w.topic_off[i]) >> 16;
+  }
+  if (lng || !small_call(idx, w.topic_off, w.n_topics, flags)) return 1;
+  if (w.n_topics && w.topic_off[w.n_topics] - w.topic_off[0] > gm::host_window_text_max()) return 1;
+  if (fan && (idx->view.gmap || idx->subs.empty() || gm::knob("GM_FANOUT_SIMPLE"))) return 1;
+  return 2;
+}
+
+// the windows in order: groups through run_host_windows (one member device
+// each, round-robin as match_small picks), the others alone; arguments checked
+// by the caller, kind[k] from window_kind.  The calling thread's stats
+// (emqx_gm_last_stats) are those of the last group or call.
+int match_windows_loop(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_window* w, uint32_t nw,
+                       const std::vector<int>& kind, uint32_t flags, emqx_gm_csr* m, emqx_gm_csr* d,
+                       uint32_t max_windows, uint64_t max_topics) {
+  int rc = EMQX_GM_OK;
+  GM_GUARD_BEGIN
+  std::vector<uint8_t> ok;
+  for (uint32_t k = 0; k < nw && rc == EMQX_GM_OK;) {
+    if (kind[k] != 2) {
+      rc = d ? emqx_gm_match_fanout(ctx, idx, w[k].topic_bytes, w[k].topic_off, w[k].n_topics, flags, &m[k], &d[k])
+             : emqx_gm_match(ctx, idx, w[k].topic_bytes, w[k].topic_off, w[k].n_topics, flags, &m[k]);
+      ++k;
+      continue;
+    }
+    uint32_t e = k;
+    uint64_t topics = 0, bytes = 0;
+    for (; e < nw && e - k < max_windows && kind[e] == 2; ++e) {
+      const uint64_t nb = w[e].n_topics ? w[e].topic_off[w[e].n_topics] - w[e].topic_off[0] : 0;
+      if (e > k && (topics + w[e].n_topics > max_topics || bytes + nb > gm::host_window_text_max())) break;
+      topics += w[e].n_topics;
+      bytes += nb;
+    }
+    const size_t K = 1 + (idx->reps.size() == ctx->members.size() ? ctx->members.size() : 0);
+    const size_t pick = K > 1 ? ctx->rr.fetch_add(1, std::memory_order_relaxed) % K : 0;
+    emqx_gm_ctx* mc = pick ? ctx->members[pick - 1] : ctx;
+    const emqx_gm_index* rix = pick ? idx->reps[pick - 1] : idx;
+    hipSetDevice(mc->device);
+    ok.assign(e - k, 0);
+    emqx_gm_match_stats st{};
+    rc = gm::run_host_windows(mc, rix, w + k, e - k, flags, m + k, d ? d + k : nullptr, ok.data(), &st);
+    if (rc == EMQX_GM_OK) {
+      tl_stats = st;
+      tl_stats_ctx = ctx;
+    }
+    hipSetDevice(ctx->device);
+    // (a window whose deliveries did not hold: today's rule, the fan-out of its rows)
+    for (uint32_t j = k; d && j < e && rc == EMQX_GM_OK; ++j)
+      if (!ok[j - k]) rc = emqx_gm_fanout(ctx, idx, &m[j], 0, &d[j]);
+    k = e;
+  }
+  return rc;
+  GM_GUARD_END(ctx)
+}
+
+// ... and on any failure (an exception included: it comes back as a code) nothing is returned or held
+int match_windows_run(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_window* w, uint32_t nw,
+                      const std::vector<int>& kind, uint32_t flags, emqx_gm_csr* m, emqx_gm_csr* d,
+                      uint32_t max_windows, uint64_t max_topics) {
+  for (uint32_t k = 0; k < nw; ++k) {
+    std::memset(&m[k], 0, sizeof(m[k]));
+    if (d) std::memset(&d[k], 0, sizeof(d[k]));
+  }
+  const int rc = match_windows_loop(ctx, idx, w, nw, kind, flags, m, d, max_windows, max_topics);
+  if (rc != EMQX_GM_OK)  // nothing is returned (the failing call's message stays)
+    for (uint32_t k = 0; k < nw; ++k) {
+      if (m[k].row_off || m[k].ids) emqx_gm_csr_free(ctx, &m[k]);
+      if (d && (d[k].row_off || d[k].ids)) emqx_gm_csr_free(ctx, &d[k]);
+      std::memset(&m[k], 0, sizeof(m[k]));
+      if (d) std::memset(&d[k], 0, sizeof(d[k]));
+    }
+  return rc;
+}
+}  // namespace
+
+int emqx_gm_match_windows(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_window* w, uint32_t n_windows,
+                          uint32_t flags, emqx_gm_csr* matches, emqx_gm_csr* deliveries) {
+  if (!ctx) return EMQX_GM_EINVAL;
+  if (!idx || (n_windows && (!w || !matches))) return gm::set_err(ctx, EMQX_GM_EINVAL, "match_windows: NULL argument");
+  if (flags & ~EMQX_GM_WITH_EXACT) return gm::set_err(ctx, EMQX_GM_EINVAL, "match_windows: flags (host buffers only)");
+  if (idx->device != ctx->device) return gm::set_err(ctx, EMQX_GM_EINVAL, "match_windows: index lives on another device");
+  std::vector<int> kind;
+  GM_GUARD_BEGIN
+  kind.resize(n_windows);
+  for (uint32_t k = 0; k < n_windows; ++k) {
+    if (w[k].n_topics && (!w[k].topic_bytes || !w[k].topic_off))
+      return gm::set_err(ctx, EMQX_GM_EINVAL, "match_windows: NULL window");
+    if (w[k].n_topics >= 0xFFFFFFF0ull) return gm::set_err(ctx, EMQX_GM_EINVAL, "match_windows: window too large");
+    if (!(kind[k] = window_kind(idx, w[k], flags, deliveries != nullptr)))
+      return gm::set_err(ctx, EMQX_GM_EINVAL, "match_windows: topic offsets not monotone");
+  }
+  GM_GUARD_END(ctx)
+  return match_windows_run(ctx, idx, w, n_windows, kind, flags, matches, deliveries, kGroupWindows,
+                           gm::host_chunk_topics());
+}
+
+// One caller's window in the combining queue (gm_combine.h): its arguments,
+// its outputs, and what its group's leader leaves for it.
+namespace {
+struct CombCall {
+  emqx_gm_window win{};
+  int kind = 2;
+  emqx_gm_csr* matches = nullptr;
+  emqx_gm_csr* deliveries = nullptr;
+  emqx_gm_match_stats stats{};  // the group's
+  std::string err;              // the leader's message, on failure
+};
+}  // namespace
+
+struct emqx_gm_combiner {
+  emqx_gm_ctx* ctx = nullptr;
+  uint32_t max_windows = kGroupWindows;
+  uint64_t max_topics = 0;
+  gm::Combiner* q = nullptr;
+  ~emqx_gm_combiner() { delete q; }
+};
+
+// a group of the queue through match_windows_run: the leader's thread runs it
+static int combiner_run(emqx_gm_combiner* cb, gm::CombWindow* const* g, uint32_t n) {
+  emqx_gm_ctx* ctx = cb->ctx;
+  const emqx_gm_index* idx = static_cast<const emqx_gm_index*>(g[0]->index);
+  const bool fan = g[0]->want_deliveries;
+  std::vector<emqx_gm_window> w(n);
+  std::vector<int> kind(n);
+  std::vector<emqx_gm_csr> m(n), d(fan ? n : 0);
+  for (uint32_t k = 0; k < n; ++k) {
+    const CombCall* c = static_cast<const CombCall*>(g[k]->user);
+    w[k] = c->win;
+    kind[k] = c->kind;
+  }
+  const int rc = match_windows_run(ctx, idx, w.data(), n, kind, g[0]->flags, m.data(), fan ? d.data() : nullptr,
+                                   cb->max_windows, cb->max_topics);
+  const char* msg = rc != EMQX_GM_OK ? emqx_gm_last_error(ctx) : nullptr;
+  for (uint32_t k = 0; k < n; ++k) {
+    CombCall* c = static_cast<CombCall*>(g[k]->user);
+    g[k]->rc = rc;
+    if (rc == EMQX_GM_OK) {
+      *c->matches = m[k];
+      if (fan) *c->deliveries = d[k];
+      c->stats = tl_stats;
+    } else if (msg) {
+      c->err = msg;
+    }
+  }
+  return 0;
+}
+
+int emqx_gm_combiner_open(emqx_gm_ctx* ctx, const emqx_gm_combiner_opts* opts, emqx_gm_combiner** out) {
+  if (!ctx) return EMQX_GM_EINVAL;
+  if (!out) return gm::set_err(ctx, EMQX_GM_EINVAL, "combiner_open: NULL out");
+  *out = nullptr;
+  GM_GUARD_BEGIN
+  gm::CombinerLimits lim;
+  lim.max_topics = gm::host_chunk_topics();
+  lim.max_bytes = gm::host_window_text_max();
+  if (opts) {
+    if (opts->max_windows > kGroupWindowsMax)
+      return gm::set_err(ctx, EMQX_GM_EINVAL, "combiner_open: max_windows (at most 256)");
+    if (opts->max_windows) lim.max_windows = opts->max_windows;
+    if (opts->max_topics) lim.max_topics = std::min<uint64_t>(opts->max_topics, lim.max_topics);
+    if (opts->max_in_flight) lim.max_in_flight = opts->max_in_flight;
+    if (opts->min_windows) lim.min_windows = opts->min_windows;
+    lim.linger_us = opts->linger_us;
+  }
+  auto* cb = new emqx_gm_combiner;
+  cb->ctx = ctx;
+  cb->max_windows = lim.max_windows;
+  cb->max_topics = lim.max_topics;
+  cb->q = new gm::Combiner(lim, [cb](gm::CombWindow* const* g, uint32_t n) { return combiner_run(cb, g, n); });
+  {  // (the context owns it: a closed combiner still answers EMQX_GM_EINVAL until emqx_gm_close)
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    ctx->combiners.push_back(cb);
+  }
+  *out = cb;
+  return EMQX_GM_OK;
+  GM_GUARD_END(ctx)
+}
+
+int emqx_gm_combiner_match(emqx_gm_combiner* cb, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to,
+                           uint64_t n, uint32_t flags, emqx_gm_csr* matches, emqx_gm_csr* deliveries) {
+  if (!cb) return EMQX_GM_EINVAL;
+  emqx_gm_ctx* ctx = cb->ctx;
+  if (!idx || !matches || (n && (!tb || !to))) return gm::set_err(ctx, EMQX_GM_EINVAL, "combiner_match: NULL argument");
+  if (flags & ~EMQX_GM_WITH_EXACT) return gm::set_err(ctx, EMQX_GM_EINVAL, "combiner_match: flags (host buffers only)");
+  if (n >= 0xFFFFFFF0ull) return gm::set_err(ctx, EMQX_GM_EINVAL, "combiner_match: batch too large (>= 2^32 topics)");
+  if (idx->device != ctx->device) return gm::set_err(ctx, EMQX_GM_EINVAL, "combiner_match: index lives on another device");
+  GM_GUARD_BEGIN
+  CombCall c;
+  c.win = emqx_gm_window{tb, to, n};
+  c.matches = matches;
+  c.deliveries = deliveries;
+  if (!(c.kind = window_kind(idx, c.win, flags, deliveries != nullptr)))
+    return gm::set_err(ctx, EMQX_GM_EINVAL, "combiner_match: topic offsets not monotone");
+  std::memset(matches, 0, sizeof(*matches));
+  if (deliveries) std::memset(deliveries, 0, sizeof(*deliveries));
+  gm::CombWindow qw;
+  qw.index = idx;
+  qw.flags = flags;
+  qw.want_deliveries = deliveries != nullptr;
+  qw.n_topics = n;
+  qw.n_bytes = n ? to[n] - to[0] : 0;
+  qw.user = &c;
+  const int rc = cb->q->submit(&qw);
+  if (rc == EMQX_GM_OK) {  // the group's figures, for this thread's emqx_gm_last_stats
+    tl_stats = c.stats;
+    tl_stats_ctx = ctx;
+    return rc;
+  }
+  return gm::set_err(ctx, rc, c.err.empty() ? "combiner_match: the combiner is closed" : c.err);
+  GM_GUARD_END(ctx)
+}
+
+int emqx_gm_combiner_stats(const emqx_gm_combiner* cb, emqx_gm_combiner_stats_t* stats) {
+  if (!cb || !stats) return EMQX_GM_EINVAL;
+  const gm::CombinerCounts c = cb->q->counts();
+  stats->windows = c.windows;
+  stats->groups = c.groups;
+  stats->max_group = c.max_group;
+  stats->solo = c.solo;
+  return EMQX_GM_OK;
+}
+
+int emqx_gm_combiner_close(emqx_gm_combiner* cb) {
+  if (!cb) return EMQX_GM_EINVAL;
+  cb->q->close();
+  return EMQX_GM_OK;
+}
+
+}  // extern "C"
+namespace gm {
+void free_combiners(emqx_gm_ctx* ctx) {
+  for (emqx_gm_combiner* cb : ctx->combiners) {
+    cb->q->close();
+    delete cb;
+  }
+  ctx->combiners.clear();
+}
+}  // namespace gm
+extern "C" {
 
 int emqx_gm_fanout_part(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_csr* m, uint32_t part,
                         uint32_t n_parts, uint32_t flags, emqx_gm_csr* out, uint64_t* first) {

@@ -1017,6 +1017,272 @@ int run_host_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb
   return 0;
 }
 
+uint64_t host_window_text_max() { return kMappedMax; }
+
+int run_host_windows(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_window* w, uint32_t g, uint32_t flags,
+                     emqx_gm_csr* matches, emqx_gm_csr* deliveries, uint8_t* fan_ok, emqx_gm_match_stats* st_out) {
+  const int nc = deliveries ? 2 : 1;  // the CSRs per window: matches, deliveries
+  uint64_t n = 0, nbytes = 0;
+  for (uint32_t k = 0; k < g; ++k) {
+    n += w[k].n_topics;
+    if (w[k].n_topics) nbytes += w[k].topic_off[w[k].n_topics] - w[k].topic_off[0];
+    matches[k] = emqx_gm_csr{};
+    if (deliveries) {
+      deliveries[k] = emqx_gm_csr{};
+      fan_ok[k] = 0;
+    }
+  }
+  // each window's results, [0] matches and [1] deliveries: page-locked, from the context's host pool
+  struct Res {
+    uint64_t* off[2] = {nullptr, nullptr};
+    uint32_t* ids[2] = {nullptr, nullptr};
+    size_t ib[2] = {0, 0};     // bytes of ids[]
+    uint64_t cap[2] = {0, 0};  // the ids k_rows_split may write
+    uint64_t len[2] = {0, 0};
+  };
+  std::vector<Res> res(g);
+  std::unique_lock<std::recursive_mutex> lk(ctx->mu, std::defer_lock);
+  auto drop_res = [&]() {  // (under the lock)
+    for (Res& r : res)
+      for (int c = 0; c < 2; ++c) {
+        ctx->hpool->release(r.off[c]);
+        ctx->hpool->release(r.ids[c]);
+        r.off[c] = nullptr;
+        r.ids[c] = nullptr;
+      }
+  };
+  auto hand_out = [&]() {  // (the results become the caller's)
+    for (uint32_t k = 0; k < g; ++k)
+      for (int c = 0; c < nc; ++c) {
+        if (c && !fan_ok[k]) continue;
+        emqx_gm_csr& o = c ? deliveries[k] : matches[k];
+        o.n_rows = w[k].n_topics;
+        o.nnz = res[k].len[c];
+        o.row_off = res[k].off[c];
+        o.ids = res[k].ids[c];
+        o.on_device = 0;
+        o.priv = ctx;  // the owning context (emqx_gm_csr_free checks it)
+      }
+  };
+  if (n == 0) {  // nothing to match: every window's empty rows, no device work
+    lk.lock();
+    for (uint32_t k = 0; k < g; ++k)
+      for (int c = 0; c < nc; ++c) {
+        res[k].off[c] = static_cast<uint64_t*>(ctx->hpool->alloc(8));
+        res[k].ids[c] = static_cast<uint32_t*>(ctx->hpool->alloc(16));
+        if (!res[k].off[c] || !res[k].ids[c]) {
+          drop_res();
+          return set_err(ctx, EMQX_GM_ENOMEM, "match_windows: host result");
+        }
+        res[k].off[c][0] = 0;
+        if (c) fan_ok[k] = 1;
+      }
+    lk.unlock();
+    if (st_out) *st_out = emqx_gm_match_stats{};
+    hand_out();
+    return 0;
+  }
+  // ---- outside the lock: the group staged in a page-locked buffer of its own:
+  // [the windows' text | 64 B of zeros | their u16 lengths | the window table]
+  const size_t o_len = (nbytes + 64 + 255) & ~size_t(255);
+  const size_t o_tab = al16(o_len + n * 2 + 2);
+  const size_t in_bytes = al16(o_tab + size_t(g) * 2 * sizeof(WinSlice));
+  PinBuf pin(ctx->pins);
+  if (!(pin.p = ctx->pins->get(in_bytes))) return set_err(ctx, EMQX_GM_ENOMEM, "match_windows: pinned staging");
+  uint8_t* in = static_cast<uint8_t*>(pin.p);
+  {
+    size_t pos = 0;
+    uint16_t* l = reinterpret_cast<uint16_t*>(in + o_len);
+    for (uint32_t k = 0; k < g; ++k) {
+      const uint64_t* to = w[k].topic_off;
+      const uint64_t nk = w[k].n_topics;
+      if (!nk) continue;
+      std::memcpy(in + pos, w[k].topic_bytes + to[0], to[nk] - to[0]);
+      pos += to[nk] - to[0];
+      for (uint64_t i = 0; i < nk; ++i) *l++ = uint16_t(to[i + 1] - to[i]);
+    }
+    std::memset(in + nbytes, 0, 64);
+  }
+  WinSlice* tab = reinterpret_cast<WinSlice*>(in + o_tab);
+  auto dev_of = [](void* h) {  // a page-locked buffer as the device addresses it
+    void* d = nullptr;
+    return hipHostGetDevicePointer(&d, h, 0) == hipSuccess ? d : nullptr;
+  };
+  // ---- under the lock: the capacities (today's rule per window: 1,024 ids plus
+  // its share; the deliveries from the context's recent deliveries per match,
+  // a power of two), the results, the table; then the group queued
+  lk.lock();
+  hipSetDevice(ctx->device);
+  hipStream_t st = ctx->stream;
+  const double ipt = std::min(ctx->ids_per_topic, double(FAST_MC));
+  const double spm = ctx->subs_per_match;
+  auto fan_want = [&](uint64_t cap) { return 1024.0 + double(cap > 1024 ? cap - 1024 : 1) * spm; };
+  const uint64_t cap_g = 1024 + uint64_t(double(n) * ipt);  // (MatchCall::submit's cap_spec for the group)
+  bool fan = deliveries && fan_want(cap_g) <= double(kFanSmallDeliveries);
+  uint64_t cap_fg = 1024;
+  while (fan && double(cap_fg) < fan_want(cap_g)) cap_fg <<= 1;
+  void* in_dev = dev_of(pin.p);
+  uint64_t max_work = 0, row0 = 0;
+  bool ok = in_dev != nullptr;
+  for (uint32_t k = 0; k < g && ok; ++k) {
+    Res& r = res[k];
+    const uint64_t nk = w[k].n_topics;
+    for (int c = 0; c < (fan ? 2 : 1); ++c) {
+      r.cap[c] = 1024 + uint64_t(double(nk) * ipt);
+      if (c)
+        for (r.cap[1] = 1024; double(r.cap[1]) < fan_want(r.cap[0]);) r.cap[1] <<= 1;
+      for (r.ib[c] = 4096; r.ib[c] < r.cap[c] * 4 + 16;) r.ib[c] <<= 1;  // (a power of two: back from the pool's cache)
+      r.off[c] = static_cast<uint64_t*>(ctx->hpool->alloc((nk + 1) * 8, true));
+      r.ids[c] = static_cast<uint32_t*>(ctx->hpool->alloc(r.ib[c], true));
+      void* d_off = r.off[c] ? dev_of(r.off[c]) : nullptr;
+      void* d_ids = r.ids[c] ? dev_of(r.ids[c]) : nullptr;
+      if (!d_off || !d_ids) ok = false;
+      tab[k * 2 + c] = WinSlice{row0, nk, r.cap[c], static_cast<uint64_t*>(d_off), static_cast<uint32_t*>(d_ids)};
+      max_work = std::max({max_work, nk + 1, (r.cap[c] + 3) / 4});
+    }
+    if (!fan) tab[k * 2 + 1] = WinSlice{};
+    row0 += nk;
+  }
+  if (!ok) {
+    drop_res();
+    return set_err(ctx, EMQX_GM_ENOMEM, "match_windows: host result");
+  }
+  void* dv[2] = {ctx->pool->alloc(in_bytes), ctx->pool->alloc((n + 1) * 8)};
+  void* fd[3] = {nullptr, nullptr, nullptr};  // the group's deliveries on the device (kept until the results are whole)
+  auto drop_dev = [&]() {  // (under the lock; the group's work is done or was never queued)
+    for (void*& q : dv)
+      if (q) ctx->pool->release(q);
+    for (void*& q : fd)
+      if (q) ctx->pool->release(q);
+    dv[0] = dv[1] = fd[0] = fd[1] = fd[2] = nullptr;
+  };
+  if (!dv[0] || !dv[1]) {
+    drop_dev();
+    drop_res();
+    return set_err(ctx, EMQX_GM_ENOMEM, "match_windows: input workspace");
+  }
+  const uint8_t* d_b = static_cast<const uint8_t*>(dv[0]);
+  const WinSlice* d_tab = reinterpret_cast<const WinSlice*>(d_b + o_tab);
+  uint64_t* d_o = static_cast<uint64_t*>(dv[1]);
+  if (launch_copy_u32x2(st, static_cast<const uint32_t*>(in_dev), static_cast<uint32_t*>(dv[0]), in_bytes / 4, nullptr,
+                        nullptr, 0) ||
+      scan_len16(ctx, st, reinterpret_cast<const uint16_t*>(d_b + o_len), n, d_o)) {
+    hipStreamSynchronize(st);
+    drop_dev();
+    drop_res();
+    return set_err(ctx, EMQX_GM_EDEVICE, "match_windows: inputs to device");
+  }
+  bool fan_q = false;
+  MatchTail tail;
+  tail.enqueue = [&](const uint64_t* d_ro, const uint32_t* d_ids, uint64_t cap) -> int {
+    if (fan) {
+      fd[0] = ctx->pool->alloc((cap + 1) * 8);
+      fd[1] = ctx->pool->alloc((n + 1) * 8);
+      fd[2] = ctx->pool->alloc(cap_fg * 4 + 16);
+      if (fd[0] && fd[1] && fd[2]) {
+        if (int frc = queue_fanout_spec(ctx, idx, d_ro, d_ids, n, cap, cap_fg, static_cast<uint64_t*>(fd[0]),
+                                        static_cast<uint64_t*>(fd[1]), static_cast<uint32_t*>(fd[2])))
+          return frc;
+        fan_q = true;
+      }  // (else no room: the caller runs its own fan-out)
+    }
+    if (launch_rows_split(st, d_tab, g, max_work, d_ro, d_ids, cap, fan_q ? static_cast<const uint64_t*>(fd[1]) : nullptr,
+                          static_cast<const uint32_t*>(fd[2]), cap_fg))
+      return set_err(ctx, EMQX_GM_EDEVICE, "match_windows: rows to host");
+    return 0;
+  };
+  void* ticket = nullptr;
+  int rc = match_submit(ctx, idx, d_b, d_o, n, flags | EMQX_GM_DEVICE_IO | EMQX_GM_NO_TIMING, &ticket, &tail);
+  if (rc) {
+    hipStreamSynchronize(st);
+    drop_dev();
+    drop_res();
+    return rc;
+  }
+  lk.unlock();
+  // ---- outside the lock: the device round trip (other callers queue theirs meanwhile)
+  emqx_gm_csr dc{};
+  rc = match_wait(ctx, ticket, &dc, &tail, st_out);
+  lk.lock();
+  if (rc) {
+    drop_dev();
+    drop_res();
+    return rc;
+  }
+  // ---- the results made whole.  The group's speculative rows held (tail.used):
+  // a window past its own capacity gets its ids from the group's device CSR,
+  // into a result of their size.  They did not: every window is cut from the
+  // true device CSR, after reading its offsets (the second round trip a small
+  // call pays then too), and the deliveries are left to the caller.
+  hipError_t x = hipSuccess;
+  std::vector<uint64_t> gro;
+  if (!tail.used) {
+    gro.resize(n + 1);
+    x = hipMemcpyAsync(gro.data(), dc.row_off, (n + 1) * 8, hipMemcpyDeviceToHost, st);
+    if (x == hipSuccess) x = hipStreamSynchronize(st);
+  }
+  bool copied = false;  // (the common case queues nothing more: no second wait)
+  auto exact_ids = [&](Res& r, int c, const uint32_t* d_src) {  // ids[c] again at len[c], copied from the device
+    if (r.len[c] * 4 + 4 > r.ib[c]) {
+      ctx->hpool->release(r.ids[c]);
+      r.ib[c] = r.len[c] * 4 + 4;
+      r.ids[c] = static_cast<uint32_t*>(ctx->hpool->alloc(r.ib[c]));
+      if (!r.ids[c]) return hipErrorOutOfMemory;
+    }
+    if (!r.len[c]) return hipSuccess;
+    copied = true;
+    return hipMemcpyAsync(r.ids[c], d_src, r.len[c] * 4, hipMemcpyDeviceToHost, st);
+  };
+  const bool fan_held = fan_q && tail.used;
+  uint64_t m0 = 0, f0 = 0;  // the window's first id / delivery in the group
+  row0 = 0;
+  for (uint32_t k = 0; k < g && x == hipSuccess; ++k) {
+    Res& r = res[k];
+    const uint64_t nk = w[k].n_topics;
+    if (tail.used) {
+      r.len[0] = r.off[0][nk];
+      if (r.len[0] > r.cap[0]) x = exact_ids(r, 0, dc.ids + m0);
+    } else {
+      for (uint64_t i = 0; i <= nk; ++i) r.off[0][i] = gro[row0 + i] - gro[row0];
+      r.len[0] = r.off[0][nk];
+      x = exact_ids(r, 0, dc.ids + gro[row0]);
+    }
+    m0 += r.len[0];
+    // (deliveries at or past the group's capacity were never written: that window's fan-out is the caller's)
+    if (fan_held) {
+      r.len[1] = r.off[1][nk];  // (the true length, whatever was written)
+      if (f0 <= cap_fg && r.len[1] <= cap_fg - f0) {
+        fan_ok[k] = 1;
+        if (r.len[1] > r.cap[1] && x == hipSuccess) x = exact_ids(r, 1, static_cast<const uint32_t*>(fd[2]) + f0);
+      }
+      f0 += r.len[1];
+    }
+    row0 += nk;
+  }
+  if (copied) {
+    const hipError_t y = hipStreamSynchronize(st);
+    if (x == hipSuccess) x = y;
+  }
+  if (fan_held && dc.nnz) ctx->subs_per_match = std::max(1.0, double(f0) / double(dc.nnz));
+  drop_dev();
+  ctx->pool->release(dc.row_off);
+  ctx->pool->release(dc.ids);
+  if (x != hipSuccess) {
+    drop_res();
+    return set_err(ctx, x == hipErrorOutOfMemory ? EMQX_GM_ENOMEM : EMQX_GM_EDEVICE, "match_windows: host result");
+  }
+  for (uint32_t k = 0; k < g; ++k)  // (deliveries that did not hold: handed back)
+    if (!deliveries || !fan_ok[k]) {
+      ctx->hpool->release(res[k].off[1]);
+      ctx->hpool->release(res[k].ids[1]);
+      res[k].off[1] = nullptr;
+      res[k].ids[1] = nullptr;
+    }
+  lk.unlock();
+  hand_out();
+  return 0;
+}
+
 
 int run_fanout_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_index* host, const emqx_gm_csr* m,
                      emqx_gm_csr* out, emqx_gm_match_stats* st_out) {

@@ -213,6 +213,7 @@ struct emqx_gm_ctx {
   std::vector<emqx_gm_ctx*> members;
   emqx_gm_ctx* parent = nullptr;    // a member: its multi-device context
   std::atomic<uint32_t> rr{0};      // round-robin start of the next small host-buffer call (gm_api.cpp)
+  std::vector<struct emqx_gm_combiner*> combiners;  // opened on this context (gm_api.cpp): freed with it
 };
 
 namespace gm {
@@ -603,6 +604,29 @@ int run_fanout_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_i
                      emqx_gm_csr* out, emqx_gm_match_stats* st_out);
 int queue_fanout_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint64_t* d_off, const uint32_t* d_ids,
                        uint64_t n, uint64_t nnz, uint64_t total, uint64_t* seg_dst, uint64_t* row_off, uint32_t* ids);
+// A group of publish windows as ONE device batch (emqx_gm_match_windows; entered
+// WITHOUT ctx->mu, like run_host_small): the windows' text and u16 lengths
+// concatenated in one page-locked staging buffer with the window table behind
+// them, one input copy, one scan, one match, the fan-out behind its
+// speculative rows when deliveries are wanted, then ONE k_rows_split launch
+// (gm_windows.hip) that cuts the group's CSRs into each window's own
+// page-locked result.  The caller has checked: every window small-call
+// eligible with monotone offsets and no topic past 65,535 B, the group within
+// host_chunk_topics() topics and host_window_text_max() bytes of text.
+// matches[k] always comes back; deliveries[k] where fan_ok[k] (else zeroed:
+// the caller fans that window's rows out itself).  On error nothing is returned.
+struct WinSlice {  // one window's part of one of the group's CSRs (the window table: [window][CSR])
+  uint64_t row0, n_rows;  // its rows in the group
+  uint64_t ids_cap;       // ids its result holds
+  uint64_t* dst_row_off;  // its result as the device addresses it: n_rows + 1 offsets from 0
+  uint32_t* dst_ids;
+};
+int launch_rows_split(hipStream_t st, const WinSlice* tab, uint32_t n_windows, uint64_t max_work, const uint64_t* ro0,
+                      const uint32_t* ids0, uint64_t cap0, const uint64_t* ro1, const uint32_t* ids1, uint64_t cap1);
+uint64_t host_window_text_max();
+void free_combiners(emqx_gm_ctx* ctx);  // gm_api.cpp: closes and frees the context's combiners (emqx_gm_close)
+int run_host_windows(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_window* w, uint32_t g, uint32_t flags,
+                     emqx_gm_csr* matches, emqx_gm_csr* deliveries, uint8_t* fan_ok, emqx_gm_match_stats* st_out);
 // gm_multi.cpp: multi-device contexts (emqx_gm_opts.n_devices).
 // A copy of flat snapshot `src` (any device) on member context m's device:
 // the host tables shared or copied, the device tables copied device to device

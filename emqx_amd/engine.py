@@ -473,6 +473,38 @@ class Context:
             lib().emqx_gm_csr_free(self.h, C.byref(m))
             lib().emqx_gm_csr_free(self.h, C.byref(d))
 
+    def match_windows(self, index: Index, windows, exact: bool = True, fanout: bool = True):
+        """Many publish windows in one call (emqx_gm_match_windows): ``windows`` is a
+        sequence of topic lists (or packed ``(bytes, offsets)`` pairs).  Returns one
+        entry per window, each what ``match_fanout`` (``fanout=True``:
+        ``((row_off, filter ids), (row_off, subscriber ids))``) or ``match``
+        (``fanout=False``: ``(row_off, filter ids)``) gives for that window alone;
+        the windows run grouped, one device round trip per group."""
+        packed = [t if isinstance(t, tuple) else pack(t) for t in windows]
+        n = len(packed)
+        w = (_lib.Window * max(n, 1))()
+        for k, (tb, to) in enumerate(packed):
+            w[k].topic_bytes, w[k].topic_off, w[k].n_topics = tb.ctypes.data, to.ctypes.data, len(to) - 1
+        m = (Csr * max(n, 1))()
+        d = (Csr * max(n, 1))() if fanout else None
+        flags = _lib.WITH_EXACT if exact else 0
+        check(lib().emqx_gm_match_windows(self.h, index.h, w, n, flags, m, d), self.h, "match_windows")
+        try:
+            if fanout:
+                return [(_csr_to_numpy(m[k]), _csr_to_numpy(d[k])) for k in range(n)]
+            return [_csr_to_numpy(m[k]) for k in range(n)]
+        finally:
+            for k in range(n):
+                lib().emqx_gm_csr_free(self.h, C.byref(m[k]))
+                if fanout:
+                    lib().emqx_gm_csr_free(self.h, C.byref(d[k]))
+
+    def combiner(self, **opts) -> "Combiner":
+        """A combining queue on this context (emqx_gm_combiner_open): concurrent
+        callers' windows coalesced into one device round trip.  Options:
+        max_windows, max_topics, max_in_flight, min_windows, linger_us."""
+        return Combiner(self, **opts)
+
     def fanout_part(self, index: Index, matches: DeviceCsr, part: int, n_parts: int) -> Tuple[DeviceCsr, int]:
         """Part ``part`` of ``n_parts`` of the fan-out of ``matches`` (emqx_gm_fanout_part):
         a device CSR whose row_off are the global delivery offsets and whose ids are the
@@ -612,6 +644,57 @@ class Context:
 
 
 # ---------------------------------------------------------------------- sharding helpers (host)
+class Combiner:
+    """emqx_gm_combiner: ``match_fanout`` / ``match`` are the context's calls of
+    the same names, blocking and thread safe; windows of callers that arrive
+    while earlier groups are on the device run as one group.  Close it before
+    its context."""
+
+    def __init__(self, ctx: Context, max_windows: int = 0, max_topics: int = 0, max_in_flight: int = 0,
+                 min_windows: int = 0, linger_us: int = 0):
+        self.ctx = ctx
+        o = _lib.CombinerOpts(max_windows=max_windows, max_topics=max_topics, max_in_flight=max_in_flight,
+                              min_windows=min_windows, linger_us=linger_us)
+        h = C.c_void_p()
+        check(lib().emqx_gm_combiner_open(ctx.h, C.byref(o), C.byref(h)), ctx.h, "combiner_open")
+        self.h = h
+
+    def _call(self, index: Index, topics, exact: bool, fanout: bool):
+        tb, to = topics if isinstance(topics, tuple) else pack(topics)
+        m, d = Csr(), Csr()
+        flags = _lib.WITH_EXACT if exact else 0
+        check(lib().emqx_gm_combiner_match(self.h, index.h, _ptr(tb), _ptr(to), len(to) - 1, flags, C.byref(m),
+                                           C.byref(d) if fanout else None), self.ctx.h, "combiner_match")
+        try:
+            return (_csr_to_numpy(m), _csr_to_numpy(d)) if fanout else _csr_to_numpy(m)
+        finally:
+            lib().emqx_gm_csr_free(self.ctx.h, C.byref(m))
+            if fanout:
+                lib().emqx_gm_csr_free(self.ctx.h, C.byref(d))
+
+    def match_fanout(self, index: Index, topics, exact: bool = True):
+        return self._call(index, topics, exact, True)
+
+    def match(self, index: Index, topics, exact: bool = True):
+        return self._call(index, topics, exact, False)
+
+    def stats(self) -> dict:
+        s = _lib.CombinerStats()
+        check(lib().emqx_gm_combiner_stats(self.h, C.byref(s)), self.ctx.h, "combiner_stats")
+        return {"windows": int(s.windows), "groups": int(s.groups), "max_group": int(s.max_group),
+                "solo": int(s.solo)}
+
+    def close(self):
+        """Waits for the calls in flight; later calls fail with EINVAL."""
+        check(lib().emqx_gm_combiner_close(self.h), self.ctx.h, "combiner_close")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 def filter_ranks(fb: np.ndarray, fo: np.ndarray) -> Tuple[np.ndarray, int]:
     """Global id of each filter = its rank among the unique filters (emqx_gm_filter_ranks)."""
     n = len(fo) - 1

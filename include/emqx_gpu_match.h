@@ -361,6 +361,87 @@ int emqx_gm_fanout(emqx_gm_ctx *ctx, const emqx_gm_index *idx, const emqx_gm_csr
 int emqx_gm_match_fanout(emqx_gm_ctx *ctx, const emqx_gm_index *idx, const uint8_t *topic_bytes,
                          const uint64_t *topic_off, uint64_t n_topics, uint32_t flags, emqx_gm_csr *matches,
                          emqx_gm_csr *deliveries);
+
+/* ---- publish windows coalesced into one device round trip ----
+ * Every scheduler of a broker node publishes at once: emqx_broker:publish/1
+ * routes and dispatches in the caller's own process
+ * (apps/emqx/src/emqx_broker.erl:204-215, 296-322) and emqx_trie:match/1 reads
+ * the shared tables from all of them concurrently (emqx_trie.erl:66-70).  Here
+ * each such caller brings one small window, and a window alone keeps the
+ * device busy for a fraction of what its chain of launches costs; the calls
+ * below run many windows as ONE device batch and hand each window its own
+ * result.
+ *
+ * emqx_gm_match_windows: n_windows host-buffer windows in one call.
+ * matches[k] -- and deliveries[k], unless deliveries is NULL (match only) -- are
+ * CSRs of their own (host pointers, row_off[0] == 0), bit-equal to what
+ * emqx_gm_match_fanout (emqx_gm_match) returns for window k alone, each freed
+ * on its own with emqx_gm_csr_free, in any order, from any thread.  flags:
+ * EMQX_GM_WITH_EXACT or 0.  Windows are grouped in order, a group being at
+ * most 64 windows, one chunk of topics (256K) and 1 MiB of text; a group makes
+ * one device round trip (one input copy, one match, the fan-out behind it, one
+ * launch that cuts the rows into the windows' results) on one device of the
+ * context, round-robin.  A window that a single call would not serve whole on
+ * one device (an overlay or sharded index, more than one chunk), one holding a
+ * topic longer than 65,535 B or more than 1 MiB of text runs alone through
+ * the ordinary call, in its place.  A NULL argument, bad flags or a window
+ * with non-monotone offsets: EMQX_GM_EINVAL before any device work, no output
+ * touched.  On any later error every output is zeroed and nothing is held. */
+typedef struct {
+  const uint8_t *topic_bytes;
+  const uint64_t *topic_off; /* n_topics + 1 entries */
+  uint64_t n_topics;
+} emqx_gm_window;
+int emqx_gm_match_windows(emqx_gm_ctx *ctx, const emqx_gm_index *idx, const emqx_gm_window *windows,
+                          uint32_t n_windows, uint32_t flags, emqx_gm_csr *matches, emqx_gm_csr *deliveries);
+
+/* emqx_gm_combiner: the same for callers that do not know of one another (a
+ * NIF's dirty schedulers).  emqx_gm_combiner_match is emqx_gm_match_fanout
+ * (deliveries != NULL) or emqx_gm_match (NULL) of the caller's window,
+ * blocking and thread safe, with the same results and errors.  A caller
+ * checks its own window (EMQX_GM_EINVAL fails that call alone) and queues it;
+ * while fewer than max_in_flight groups are on the device it becomes a
+ * leader, takes every queued window of the same index, flags and
+ * deliveries-or-not up to the group limits, runs them through
+ * emqx_gm_match_windows and hands each caller its own CSRs and return code; a
+ * leader's failure reaches every member of its group.  What stays queued is
+ * led by one of its owners next.  With the defaults a lone caller never
+ * waits: coalescing comes only from what queued while earlier groups were on
+ * the device.  Every setting is in the opts (0: the default); there is no
+ * environment knob.
+ *   max_windows   windows per group (default 64, at most 256)
+ *   max_topics    topics per group (default and most: one chunk, 256K)
+ *   max_in_flight groups on the device at once (default 2)
+ *   min_windows, linger_us   a leader waits until min_windows windows have
+ *                 arrived or linger_us has passed (defaults 1 and 0: no wait;
+ *                 for tests and tuning)
+ * After a combiner call emqx_gm_last_stats(ctx) reports, to the calling
+ * thread, the figures of the GROUP its window ran in (n_topics and nnz of the
+ * whole group), not of the window alone.  emqx_gm_combiner_close waits for
+ * the calls in flight; calls after it return EMQX_GM_EINVAL (close it before
+ * the context, and let no call start once it returns). */
+typedef struct emqx_gm_combiner emqx_gm_combiner;
+typedef struct {
+  uint32_t max_windows;
+  uint64_t max_topics;
+  uint32_t max_in_flight;
+  uint32_t min_windows;
+  uint32_t linger_us;
+  uint64_t reserved[2];
+} emqx_gm_combiner_opts;
+typedef struct {
+  uint64_t windows;   /* calls queued                                        */
+  uint64_t groups;    /* groups run                                          */
+  uint64_t max_group; /* windows of the largest group                        */
+  uint64_t solo;      /* groups of one window                                */
+} emqx_gm_combiner_stats_t;
+int emqx_gm_combiner_open(emqx_gm_ctx *ctx, const emqx_gm_combiner_opts *opts, emqx_gm_combiner **out);
+int emqx_gm_combiner_match(emqx_gm_combiner *cb, const emqx_gm_index *idx, const uint8_t *topic_bytes,
+                           const uint64_t *topic_off, uint64_t n_topics, uint32_t flags, emqx_gm_csr *matches,
+                           emqx_gm_csr *deliveries);
+int emqx_gm_combiner_stats(const emqx_gm_combiner *cb, emqx_gm_combiner_stats_t *stats);
+int emqx_gm_combiner_close(emqx_gm_combiner *cb);
+
 int emqx_gm_csr_free(emqx_gm_ctx *ctx, emqx_gm_csr *csr);
 int emqx_gm_last_stats(const emqx_gm_ctx *ctx, emqx_gm_match_stats *stats);
 

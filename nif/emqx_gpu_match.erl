@@ -23,10 +23,20 @@
 %% [0,1,2,3,4,5,6,7]; a single ordinal is one GPU).  With a list, the one NIF
 %% context replicates every index to all of them and spreads each batch over
 %% them (emqx_gm_opts.n_devices).
+%% `gpu_match_coalesce` (default false): LoadInfo becomes {coalesce, Devices}
+%% and the NIF opens one emqx_gm_combiner on its context; match_batch/2,
+%% match_routes_batch/2 and fanout_batch/2 then go through it, so the windows
+%% of dirty schedulers that call at once -- every publisher matches in its own
+%% process, emqx_broker.erl:204-215, emqx_trie.erl:66-70 -- share one device
+%% round trip.  Results are the same either way.
 init() ->
     Priv = case code:priv_dir(emqx) of {error, _} -> "priv"; D -> D end,
     Devices = application:get_env(emqx, gpu_match_devices, 0),
-    erlang:load_nif(filename:join(Priv, "emqx_gpu_match_nif"), Devices).
+    Info = case application:get_env(emqx, gpu_match_coalesce, false) of
+               true -> {coalesce, Devices};
+               _ -> Devices
+           end,
+    erlang:load_nif(filename:join(Priv, "emqx_gpu_match_nif"), Info).
 
 %% The route filters (emqx_route topics; wildcard ones are the emqx_trie
 %% entries) -> an immutable index snapshot in HBM.

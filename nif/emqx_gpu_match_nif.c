@@ -41,6 +41,10 @@ typedef struct {
 
 static ErlNifResourceType *INDEX_RT, *RETAINED_RT, *SHARED_RT, *AUTHZ_RT;
 static emqx_gm_ctx *CTX;
+/* LoadInfo {coalesce, Devices}: the context's one combining queue -- the
+ * windows of dirty schedulers calling at once run as one device batch
+ * (emqx_gm_combiner, defaults); NULL: every call makes its own round trip */
+static emqx_gm_combiner *COMB;
 static ERL_NIF_TERM A_OK, A_ERROR, A_BADARG, A_INSERT, A_DELETE, A_SUBSCRIBE, A_UNSUBSCRIBE, A_ROUTE_ADD,
     A_ROUTE_DELETE, A_UNDEFINED;
 
@@ -75,11 +79,18 @@ static void authz_dtor(ErlNifEnv *env, void *obj) {
  * batch over them (emqx_gm_opts.n_devices), as the reference's match_routes/1
  * runs on all schedulers at once (emqx_trie.erl:66-70, emqx_router.erl:128-145). */
 static int load(ErlNifEnv *env, void **priv, ERL_NIF_TERM info) {
-  int device = 0;
+  int device = 0, arity = 0, coalesce = 0;
   unsigned nl = 0;
+  const ERL_NIF_TERM *tup;
   emqx_gm_opts o;
   (void)priv;
   memset(&o, 0, sizeof(o));
+  /* {coalesce, Devices}: Devices as below, the calls through one combiner */
+  if (enif_get_tuple(env, info, &arity, &tup)) {
+    if (arity != 2 || !enif_is_identical(tup[0], enif_make_atom(env, "coalesce"))) return 1;
+    coalesce = 1;
+    info = tup[1];
+  }
   if (enif_get_list_length(env, info, &nl) && nl > 0) {
     ERL_NIF_TERM h, t = info;
     if (nl > EMQX_GM_MAX_DEVICES) return 1;
@@ -105,12 +116,15 @@ static int load(ErlNifEnv *env, void **priv, ERL_NIF_TERM info) {
   A_UNSUBSCRIBE = enif_make_atom(env, "unsubscribe");
   A_ROUTE_ADD = enif_make_atom(env, "route_add");
   A_ROUTE_DELETE = enif_make_atom(env, "route_delete");
-  return emqx_gm_open(&o, &CTX) == EMQX_GM_OK && INDEX_RT && RETAINED_RT && SHARED_RT && AUTHZ_RT ? 0 : 1;
+  if (emqx_gm_open(&o, &CTX) != EMQX_GM_OK || !INDEX_RT || !RETAINED_RT || !SHARED_RT || !AUTHZ_RT) return 1;
+  if (coalesce && emqx_gm_combiner_open(CTX, NULL, &COMB) != EMQX_GM_OK) return 1;
+  return 0;
 }
 
 static void unload(ErlNifEnv *env, void *priv) {
   (void)env;
   (void)priv;
+  if (COMB) emqx_gm_combiner_close(COMB); /* (waits for the calls in flight; the context frees it) */
   if (CTX) emqx_gm_close(CTX);
 }
 
@@ -390,7 +404,8 @@ static ERL_NIF_TERM do_match(ErlNifEnv *env, const ERL_NIF_TERM argv[], uint32_t
   int rc;
   if (!enif_get_resource(env, argv[0], INDEX_RT, (void **)&r)) return enif_make_badarg(env);
   if (!pack_topics(env, argv[1], &tb, &to, &n)) return enif_make_badarg(env);
-  rc = emqx_gm_match(CTX, r->idx, tb, to, n, flags, &out);
+  rc = COMB ? emqx_gm_combiner_match(COMB, r->idx, tb, to, n, flags, &out, NULL)
+            : emqx_gm_match(CTX, r->idx, tb, to, n, flags, &out);
   free_topics(tb, to);
   if (rc != EMQX_GM_OK) return error_tuple(env, rc);
   /* each filter is a binary over the snapshot's own host bytes, kept alive by the resource */
@@ -440,8 +455,10 @@ static ERL_NIF_TERM fanout_batch(ErlNifEnv *env, int argc, const ERL_NIF_TERM ar
   (void)argc;
   if (!enif_get_resource(env, argv[0], INDEX_RT, (void **)&r)) return enif_make_badarg(env);
   if (!pack_topics(env, argv[1], &tb, &to, &n)) return enif_make_badarg(env);
-  /* the match and its fan-out in one call: one device round trip per window */
-  rc = emqx_gm_match_fanout(CTX, r->idx, tb, to, n, EMQX_GM_WITH_EXACT, &m, &d);
+  /* the match and its fan-out in one call: one device round trip per window,
+   * or (coalesce) per group of the windows that call at once */
+  rc = COMB ? emqx_gm_combiner_match(COMB, r->idx, tb, to, n, EMQX_GM_WITH_EXACT, &m, &d)
+            : emqx_gm_match_fanout(CTX, r->idx, tb, to, n, EMQX_GM_WITH_EXACT, &m, &d);
   free_topics(tb, to);
   if (rc != EMQX_GM_OK) return error_tuple(env, rc);
   rows = enif_alloc(sizeof(ERL_NIF_TERM) * (n ? n : 1));
