@@ -106,6 +106,23 @@ class Forwards(C.Structure):
                 ("priv", C.c_void_p)]
 
 
+class PublishOpts(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("shared", C.c_void_p), ("strategy", C.c_uint32), ("seed", C.c_uint32),
+                ("msg_hash", C.c_void_p), ("dests", C.c_void_p), ("skip_node", C.c_uint32),
+                ("reserved", C.c_uint64 * 2)]
+
+
+class PublishResult(C.Structure):
+    _fields_ = [("matches", Csr), ("deliveries", Csr), ("pick_members", Csr), ("pick_slots", Csr),
+                ("forwards", Forwards)]
+
+
+class PublishStats(C.Structure):
+    _fields_ = [("device_waits", C.c_uint32), ("rows_spec", C.c_uint8), ("fanout_spec", C.c_uint8),
+                ("picks_spec", C.c_uint8), ("forwards_spec", C.c_uint8), ("n_hits", C.c_uint64),
+                ("n_pairs", C.c_uint64), ("cap_hits", C.c_uint64), ("cap_pairs", C.c_uint64)]
+
+
 class AuthzDesc(C.Structure):
     _fields_ = [("n_segments", C.c_uint32), ("seg_kind", C.c_void_p), ("seg_range_off", C.c_void_p),
                 ("n_ranges", C.c_uint64), ("range_rule_off", C.c_void_p), ("key_bytes", C.c_void_p),
@@ -199,6 +216,9 @@ SIGNATURES = {
     "emqx_gm_forwards_free": (_i32, [_vp, C.POINTER(Forwards)]),
     "emqx_gm_dests_info": (_i32, [_vp, C.POINTER(DestsInfo)]),
     "emqx_gm_dests_release": (_i32, [_vp]),
+    "emqx_gm_publish_window": (_i32, [_vp, _vp, _vp, _vp, _u64, C.POINTER(PublishOpts), C.POINTER(PublishResult),
+                                      C.POINTER(PublishStats)]),
+    "emqx_gm_publish_result_free": (_i32, [_vp, C.POINTER(PublishResult)]),
     "emqx_gm_authz_build": (_i32, [_vp, C.POINTER(AuthzDesc), _u32, C.POINTER(_vp)]),
     "emqx_gm_authz_check": (_i32, [_vp, _vp, C.POINTER(AuthzBatch), _u32, _vp, _vp]),
     "emqx_gm_authz_info": (_i32, [_vp, C.POINTER(AuthzInfo)]),

@@ -175,6 +175,10 @@ class GpuRoutes:
         # (the NIF's fanout_batch/2: emqx_gm_match_fanout, the match and its fan-out in one call)
         # (with a combiner: the same call, coalesced with the windows of concurrent callers)
         (ro, ids), (fro, fids) = (self.combiner or self.ctx).match_fanout(idx, list(topics), exact=True)
+        return self._cut(idx, ro, ids, fro, fids), idx, (ro, ids)
+
+    def _cut(self, idx, ro, ids, fro, fids) -> List[Row]:
+        """Each fan-out row cut back into one segment per matched filter."""
         out = []
         for k in range(len(ro) - 1):
             row, pos = [], int(fro[k])
@@ -187,7 +191,27 @@ class GpuRoutes:
                 pos += c
             assert pos == int(fro[k + 1])
             out.append(row)
-        return out, idx, (ro, ids)
+        return out
+
+    def window(self, topics: Sequence[bytes], shared=None, strategy="round_robin", hashes=None, cluster=None):
+        """``groups_rows`` plus the window's shared picks (``shared``, a SharedSub:
+        what its ``dispatch_batch`` gives, same per-call seed rule) and forward
+        plan (``cluster``, a ClusterRoutes: what its ``plan`` gives) from ONE
+        ``Context.publish_window`` call -- one device round trip where the three
+        calls make five waits.  Returns (rows, snapshot, (row_off, filter ids),
+        picks per row or None, ForwardPlan or None, stats)."""
+        self.refresh()
+        if self.stale:
+            raise RuntimeError("stale_index")
+        idx = self.index
+        st = shared.table(idx) if shared is not None else None
+        dt = cluster.table(idx) if cluster is not None else None
+        (ro, ids), (fro, fids), picks, plan, stats = self.ctx.publish_window(
+            idx, list(topics), exact=True, shared=st, strategy=strategy, hashes=hashes,
+            seed=shared.next_seed() if shared is not None else 0, dests=dt,
+            skip_node=cluster.self_id if cluster is not None else None)
+        rows = self._cut(idx, ro, ids, fro, fids)
+        return rows, idx, (ro, ids), (shared.picks_rows(*picks) if shared is not None else None), plan, stats
 
 
 class PublishBatcher:
@@ -229,7 +253,12 @@ class PublishBatcher:
     exception: ("error", "badrpc")) is recorded as the result of each of its
     pairs.  ``lookup_routes`` is then consulted for group destinations only.
     A message's forwards leave with its window, so ``submit`` takes the
-    message too.  Without ``cluster`` nothing changes."""
+    message too.  Without ``cluster`` nothing changes.
+
+    ``one_call`` (needs ``routes``; used when ``shared`` or ``cluster`` is
+    given): the window's rows, picks and plan come from ONE ``routes.window``
+    call (emqx_gm_publish_window: one device round trip) instead of the three
+    calls above; the results are the same."""
 
     def __init__(self, groups_fn: Optional[Callable[[Sequence[bytes]], List[Row]]] = None, max_batch: int = 4096,
                  window_s: float = 0.001, subscribers: Optional[Dict[int, object]] = None,
@@ -244,7 +273,8 @@ class PublishBatcher:
                  persist: Optional[Callable[[bytes, object], None]] = None,
                  routes: Optional[GpuRoutes] = None, shared=None, shared_strategy: str = "round_robin",
                  shared_hash: Optional[Callable[[bytes, object], int]] = None, cluster=None,
-                 forward_batch: Optional[Callable[[bytes, List[Tuple[bytes, object]]], object]] = None):
+                 forward_batch: Optional[Callable[[bytes, List[Tuple[bytes, object]]], object]] = None,
+                 one_call: bool = False):
         if routes is None and isinstance(getattr(groups_fn, "__self__", None), GpuRoutes):
             routes = groups_fn.__self__
         if groups_fn is None:
@@ -260,6 +290,9 @@ class PublishBatcher:
             raise TypeError("PublishBatcher(shared=...) needs routes (the window's matched rows)")
         if cluster is not None and routes is None:
             raise TypeError("PublishBatcher(cluster=...) needs routes (the window's matched rows)")
+        if one_call and routes is None:
+            raise TypeError("PublishBatcher(one_call=True) needs routes (the window call)")
+        self.one_call = one_call
         self.routes, self.shared, self.shared_strategy = routes, shared, shared_strategy
         self.cluster = cluster
         self.forward_batch = forward_batch or (lambda node, pairs: ("error", "badrpc"))
@@ -354,25 +387,35 @@ class PublishBatcher:
     def _rows(self, topics: Sequence[bytes], msgs: Optional[Sequence[object]] = None):
         try:
             if self.shared is not None or self.cluster is not None:
-                rows, idx, csr = self.routes.groups_rows(list(topics))
                 msgs = msgs if msgs is not None else [None] * len(topics)
-                picks = [None] * len(rows)
-                if self.shared is not None:  # the window's shared picks: one device call
-                    hashes = None
-                    if self.shared_strategy.startswith("hash"):
-                        hashes = [self.shared_hash(t, m) & 0xFFFFFFFF for t, m in zip(topics, msgs)]
-                    picks = self.shared.dispatch_batch(idx, csr, self.shared_strategy, hashes)
+                hashes = None
+                if self.shared is not None and self.shared_strategy.startswith("hash"):
+                    hashes = [self.shared_hash(t, m) & 0xFFFFFFFF for t, m in zip(topics, msgs)]
+                plan = None
+                if self.one_call:  # rows, picks and plan: one device call
+                    rows, idx, csr, picks, plan, _ = self.routes.window(
+                        list(topics), shared=self.shared, strategy=self.shared_strategy, hashes=hashes,
+                        cluster=self.cluster)
+                    if picks is None:
+                        picks = [None] * len(rows)
+                else:
+                    rows, idx, csr = self.routes.groups_rows(list(topics))
+                    picks = [None] * len(rows)
+                    if self.shared is not None:  # the window's shared picks: one device call
+                        picks = self.shared.dispatch_batch(idx, csr, self.shared_strategy, hashes)
                 if self.cluster is None:
                     return [("ok", r, p) for r, p in zip(rows, picks)]
-                return [("ok", r, p, w) for r, p, w in zip(rows, picks, self._forward_window(idx, csr, msgs))]
+                return [("ok", r, p, w) for r, p, w in zip(rows, picks, self._forward_window(idx, csr, msgs, plan))]
             return [("ok", r) for r in self.groups_fn(list(topics))]
         except Exception as e:  # the NIF's {error, _}: every caller takes the reference path
             return [("error", str(e))] * len(topics)
 
-    def _forward_window(self, idx, csr, msgs):
-        """The window's remote node routes: one plan call, one forward_batch per
-        node with work.  Per row, [(node, filter, result)]."""
-        plan = self.cluster.plan(idx, csr)
+    def _forward_window(self, idx, csr, msgs, plan=None):
+        """The window's remote node routes: one plan call (or the window call's
+        ``plan``), one forward_batch per node with work.  Per row, [(node,
+        filter, result)]."""
+        if plan is None:
+            plan = self.cluster.plan(idx, csr)
         names: Dict[int, bytes] = {}
         out: List[list] = [[] for _ in msgs]
         for k in range(len(plan.node_off) - 1):

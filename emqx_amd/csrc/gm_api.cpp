@@ -12,7 +12,10 @@
 #include <sys/mman.h>
 
 #include "gm_combine.h"
+#include "gm_dests.h"
 #include "gm_internal.h"
+#include "gm_publish.h"
+#include "gm_shared.h"
 #include "../../include/emqx_gm_ext.h"
 
 namespace gm {
@@ -811,6 +814,101 @@ int emqx_gm_match_fanout(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8
   rc = emqx_gm_fanout(ctx, idx, matches, 0, deliveries);
   if (rc != EMQX_GM_OK) emqx_gm_csr_free(ctx, matches);  // (the error message stays the fan-out's)
   return rc;
+}
+
+
+// ---- a whole publish window in one device round trip (gm_publish.hip) ----
+int emqx_gm_publish_result_free(emqx_gm_ctx* ctx, emqx_gm_publish_result* res) {
+  if (!ctx || !res) return EMQX_GM_EINVAL;
+  for (emqx_gm_csr* c : {&res->matches, &res->deliveries, &res->pick_members, &res->pick_slots})
+    if (c->row_off || c->ids) emqx_gm_csr_free(ctx, c);
+  if (res->forwards.node_off || res->forwards.rows || res->forwards.filters || res->forwards.row_routes)
+    emqx_gm_forwards_free(ctx, &res->forwards);
+  std::memset(res, 0, sizeof(*res));
+  return EMQX_GM_OK;
+}
+
+int emqx_gm_publish_window(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to,
+                           uint64_t n, const emqx_gm_publish_opts* o, emqx_gm_publish_result* out,
+                           emqx_gm_publish_stats* stats) {
+  if (!ctx) return EMQX_GM_EINVAL;
+  // every argument checked before any device work, no output touched
+  if (!idx || !o || !out || (n && (!tb || !to)))
+    return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window: NULL argument");
+  if (o->flags & ~EMQX_GM_WITH_EXACT)
+    return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window: flags (host buffers only)");
+  if (n >= 0xFFFFFFF0ull) return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window: batch too large (>= 2^32 topics)");
+  if (idx->device != ctx->device)
+    return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window: index lives on another device");
+  for (uint64_t i = 0; i < n; ++i)
+    if (to[i + 1] < to[i]) return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window: topic offsets not monotone");
+  if (emqx_gm_shared* sh = o->shared) {
+    if (o->strategy > EMQX_GM_SHARE_RANDOM) return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window: strategy");
+    if (!sh->dev_base) return gm::set_err(ctx, EMQX_GM_EUNSUPPORTED, "publish_window: a host-only shared table");
+    if (sh->device != ctx->device)
+      return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window: the shared table is on another device");
+    if (sh->idx != idx)
+      return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window: the shared table is bound to another snapshot");
+    if (o->strategy == EMQX_GM_SHARE_HASH && !o->msg_hash && n)
+      return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window: msg_hash is required for EMQX_GM_SHARE_HASH");
+  }
+  if (emqx_gm_dests* dt = o->dests) {
+    if (!dt->dev_base) return gm::set_err(ctx, EMQX_GM_EUNSUPPORTED, "publish_window: a host-only dests table");
+    if (dt->device != ctx->device)
+      return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window: the dests table is on another device");
+    if (dt->idx != idx)
+      return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window: the dests table is bound to another snapshot");
+  }
+  std::memset(out, 0, sizeof(*out));
+  emqx_gm_publish_stats st{};
+  int rc = EMQX_GM_OK;
+  auto fail = [&](int code) {  // every output zeroed, nothing held (the failing call's message stays)
+    emqx_gm_publish_result_free(ctx, out);
+    return code;
+  };
+  GM_GUARD_BEGIN
+  if (small_call(idx, to, n, o->flags) && !idx->view.gmap && !idx->subs.empty() && !gm::knob("GM_FANOUT_SIMPLE")) {
+    // the window whole on this context's own device (the first listed: it holds the side tables)
+    gm::PwArgs a;
+    a.sh = o->shared;
+    a.strategy = o->strategy;
+    a.seed = o->seed;
+    a.msg_hash = o->msg_hash;
+    a.dt = o->dests;
+    a.skip_node = o->skip_node;
+    gm::SmallFan fan;
+    emqx_gm_match_stats ms{};
+    hipSetDevice(ctx->device);
+    rc = gm::run_publish_window(ctx, idx, tb, to, n, o->flags, a, out, &st, &ms, &fan);
+    if (rc != EMQX_GM_OK) return fail(rc);
+    tl_stats = ms;
+    tl_stats_ctx = ctx;
+    if (fan.ok) {
+      out->deliveries = fan.out;
+      st.fanout_spec = 1;
+    } else {  // (emqx_gm_match_fanout's rule: the fan-out of the returned rows)
+      rc = emqx_gm_fanout(ctx, idx, &out->matches, 0, &out->deliveries);
+      if (rc != EMQX_GM_OK) return fail(rc);
+      st.device_waits += 1;
+    }
+  } else {  // not a one-round-trip window: the three calls in sequence (their waits are not counted)
+    rc = emqx_gm_match_fanout(ctx, idx, tb, to, n, o->flags, &out->matches, &out->deliveries);
+    if (rc != EMQX_GM_OK) return fail(rc);
+    if (o->shared) {
+      rc = emqx_gm_shared_pick(ctx, o->shared, &out->matches, o->strategy, o->msg_hash, o->seed, &out->pick_members,
+                               &out->pick_slots);
+      if (rc != EMQX_GM_OK) return fail(rc);
+      st.n_hits = out->pick_members.nnz;
+    }
+    if (o->dests) {
+      rc = emqx_gm_forward_plan(ctx, o->dests, &out->matches, o->skip_node, &out->forwards);
+      if (rc != EMQX_GM_OK) return fail(rc);
+      st.n_pairs = out->forwards.n_pairs;
+    }
+  }
+  GM_GUARD_END(ctx)
+  if (stats) *stats = st;
+  return EMQX_GM_OK;
 }
 
 // ---- publish windows coalesced into one device round trip (emqx_gm_match_windows,

@@ -93,6 +93,21 @@ int dt_plan_host(const emqx_gm_dests* dt, const emqx_gm_csr* m, uint32_t skip_no
 // gm_dests.hip (device)
 int dt_upload(emqx_gm_ctx* ctx, emqx_gm_dests* dt);
 void dt_free_device(emqx_gm_dests* dt);
+// host_out: device rows in, the result on the host (a publish window's
+// rerun); waits (optional): += the host-blocking device waits made
 int dt_plan_device(emqx_gm_ctx* ctx, emqx_gm_dests* dt, const emqx_gm_csr* m, uint32_t skip_node, uint32_t n_chunks,
-                   emqx_gm_forwards* out);
+                   emqx_gm_forwards* out, bool host_out = false, uint32_t* waits = nullptr);
+// A plan queued over a small call's speculative rows (emqx_gm_publish_window):
+// device pointers into one workspace `ws` of the context's pool, which the
+// caller releases behind the stream; *total is the true pair count.
+struct DtSpec {
+  void* ws = nullptr;
+  uint32_t* row_routes = nullptr;  // [n]
+  uint64_t* node_off = nullptr;    // [n_nodes + 1]
+  uint32_t* rows = nullptr;        // [cap_pairs]
+  uint32_t* filters = nullptr;     // [cap_pairs]
+  const uint64_t* total = nullptr;
+};
+int dt_queue_spec(emqx_gm_ctx* ctx, emqx_gm_dests* dt, const uint64_t* d_ro, const uint32_t* d_ids, uint64_t n,
+                  uint64_t cap, uint64_t cap_pairs, uint32_t skip_node, DtSpec* out);
 }  // namespace gm

@@ -65,10 +65,17 @@ __global__ __launch_bounds__(256) void k_fw_row_routes(DtView v, const uint64_t*
   row_routes[r] = all < 0xFFFFFFFFull ? uint32_t(all) : 0xFFFFFFFFu;
 }
 
+// nnz_p (optional, speculative rows: nnz is their capacity): the rows' own count
+// on the device; an entry past it counts 0, so k_fw_expand skips it too
 __global__ __launch_bounds__(256) void k_fw_count(DtView v, const uint32_t* __restrict__ ids, uint64_t nnz,
-                                                  uint32_t skip_node, uint64_t* __restrict__ cnt) {
+                                                  const uint64_t* __restrict__ nnz_p, uint32_t skip_node,
+                                                  uint64_t* __restrict__ cnt) {
   const uint64_t j = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (j >= nnz) return;
+  if (nnz_p && j >= *nnz_p) {
+    cnt[j] = 0;
+    return;
+  }
   const uint32_t f = ids[j];
   uint32_t c = 0;
   if (f < v.n_filters) {
@@ -231,10 +238,14 @@ void dt_free_device(emqx_gm_dests* dt) {
 }
 
 int dt_plan_device(emqx_gm_ctx* ctx, emqx_gm_dests* dt, const emqx_gm_csr* m, uint32_t skip_node, uint32_t n_chunks,
-                   emqx_gm_forwards* out) {
+                   emqx_gm_forwards* out, bool host_out, uint32_t* waits) {
   GM_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const bool dev = m->on_device != 0;
+  // (host_out: device rows, but a host result -- a publish window's rerun, gm_publish.hip)
+  const bool dev_in = m->on_device != 0, dev = dev_in && !host_out;
+  auto waited = [&]() {
+    if (waits) ++*waits;
+  };
   const uint64_t n = m->n_rows, nnz = m->nnz;
   const uint32_t N = dt->hv.n_nodes;
   auto res_alloc = [&](size_t bytes) -> void* {
@@ -257,6 +268,7 @@ int dt_plan_device(emqx_gm_ctx* ctx, emqx_gm_dests* dt, const emqx_gm_csr* m, ui
     if (dev) {
       GM_HIP(ctx, hipMemsetAsync(out->node_off, 0, (uint64_t(N) + 1) * 8, st));
       GM_HIP(ctx, hipStreamSynchronize(st));
+      waited();
     } else {
       std::fill(out->node_off, out->node_off + N + 1, uint64_t(0));
     }
@@ -276,15 +288,18 @@ int dt_plan_device(emqx_gm_ctx* ctx, emqx_gm_dests* dt, const emqx_gm_csr* m, ui
   const uint64_t* d_mro = m->row_off;
   const uint32_t* d_mids = m->ids;
   uint32_t* d_rr = out->row_routes;
-  if (!dev) {
+  if (!dev_in) {
     b_ro = PoolBuf(ctx->pool, (n + 1) * 8);
     b_ids = PoolBuf(ctx->pool, nnz * 4);
-    b_rr = PoolBuf(ctx->pool, n * 4);
-    if (!b_ro.p || !b_ids.p || !b_rr.p) return set_err(ctx, EMQX_GM_ENOMEM, "forward_plan: device buffers");
+    if (!b_ro.p || !b_ids.p) return set_err(ctx, EMQX_GM_ENOMEM, "forward_plan: device buffers");
     GM_HIP(ctx, hipMemcpyAsync(b_ro.p, m->row_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
     GM_HIP(ctx, hipMemcpyAsync(b_ids.p, m->ids, nnz * 4, hipMemcpyHostToDevice, st));
     d_mro = b_ro.as<uint64_t>();
     d_mids = b_ids.as<uint32_t>();
+  }
+  if (!dev) {
+    b_rr = PoolBuf(ctx->pool, n * 4);
+    if (!b_rr.p) return set_err(ctx, EMQX_GM_ENOMEM, "forward_plan: device buffers");
     d_rr = b_rr.as<uint32_t>();
   }
   PoolBuf d_cnt(ctx->pool, nnz * 8), d_hoff(ctx->pool, (nnz + 1) * 8);
@@ -295,8 +310,8 @@ int dt_plan_device(emqx_gm_ctx* ctx, emqx_gm_dests* dt, const emqx_gm_csr* m, ui
   // enumerate
   hipLaunchKernelGGL(k_fw_row_routes, dim3(blocks_of(n)), dim3(256), 0, st, dt->dv, d_mro, n, d_mids, nnz, d_rr);
   GM_HIP(ctx, hipGetLastError());
-  hipLaunchKernelGGL(k_fw_count, dim3(blocks_of(nnz)), dim3(256), 0, st, dt->dv, d_mids, nnz, skip_node,
-                     d_cnt.as<uint64_t>());
+  hipLaunchKernelGGL(k_fw_count, dim3(blocks_of(nnz)), dim3(256), 0, st, dt->dv, d_mids, nnz,
+                     static_cast<const uint64_t*>(nullptr), skip_node, d_cnt.as<uint64_t>());
   GM_HIP(ctx, hipGetLastError());
   if (const int rc = scan_lengths(ctx, d_cnt.as<uint64_t>(), nnz, d_hoff.as<uint64_t>())) return rc;
   GM_HIP(ctx, hipEventRecord(ev.e[1], st));
@@ -304,6 +319,7 @@ int dt_plan_device(emqx_gm_ctx* ctx, emqx_gm_dests* dt, const emqx_gm_csr* m, ui
   GM_HIP(ctx, hipMemcpyAsync(&hits, d_hoff.as<uint64_t>() + nnz, 8, hipMemcpyDeviceToHost, st));
   if (!dev) GM_HIP(ctx, hipMemcpyAsync(out->row_routes, d_rr, n * 4, hipMemcpyDeviceToHost, st));
   GM_HIP(ctx, hipStreamSynchronize(st));
+  waited();
   if (hits >= 0xFFFFFFFFull) return set_err(ctx, EMQX_GM_EOVERFLOW, "forward_plan: 2^32 - 1 hits or more in one call");
   if (!hits) return no_pairs();  // (every route of the window is skip_node's: row_routes still counts them)
   out->n_pairs = hits;
@@ -363,6 +379,7 @@ int dt_plan_device(emqx_gm_ctx* ctx, emqx_gm_dests* dt, const emqx_gm_csr* m, ui
   }
   GM_HIP(ctx, hipEventRecord(ev.e[4], st));
   GM_HIP(ctx, hipStreamSynchronize(st));
+  waited();
   float ms[4] = {0, 0, 0, 0};
   for (int k = 0; k < 3; ++k) GM_HIP(ctx, hipEventElapsedTime(&ms[k], ev.e[k], ev.e[k + 1]));
   GM_HIP(ctx, hipEventElapsedTime(&ms[3], ev.e[0], ev.e[4]));
@@ -372,6 +389,77 @@ int dt_plan_device(emqx_gm_ctx* ctx, emqx_gm_dests* dt, const emqx_gm_csr* m, ui
   }
   undo.armed = false;
   return EMQX_GM_OK;
+}
+
+
+// The plan of a small call's SPECULATIVE rows (gm_publish.hip), queued on the
+// context stream with no wait and no read-back: the counts run over the ids'
+// capacity `cap` with the rows' own count read on the device (d_ro + n), the
+// expansion into cap_pairs hits (h_node pre-filled FW_NONE, so the partition
+// skips the unused ones; its chunking is fixed from cap_pairs).  1: not queued.
+int dt_queue_spec(emqx_gm_ctx* ctx, emqx_gm_dests* dt, const uint64_t* d_ro, const uint32_t* d_ids, uint64_t n,
+                  uint64_t cap, uint64_t cap_pairs, uint32_t skip_node, DtSpec* out) {
+  hipStream_t st = ctx->stream;
+  const uint32_t N = dt->hv.n_nodes;
+  if (!N || !n || !cap || !cap_pairs) return 1;  // (nothing to plan: the exact call answers without a kernel)
+  uint32_t C = uint32_t(std::min<uint64_t>(fw_chunks(cap_pairs, N), cap_pairs));
+  const uint64_t L = (cap_pairs + C - 1) / C;
+  C = uint32_t((cap_pairs + L - 1) / L);
+  // one workspace: cnt | hoff | row routes | hit rows | hit filters | hit nodes | hist | totals | node_off | rows | filters
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += align_up(std::max<size_t>(bytes, 16), 256);
+    return at;
+  };
+  const size_t o_cnt = take(cap * 8), o_hoff = take((cap + 1) * 8), o_rr = take(n * 4);
+  const size_t o_hrow = take(cap_pairs * 4), o_hfil = take(cap_pairs * 4), o_hnode = take(cap_pairs * 4);
+  const size_t o_hist = take(uint64_t(C) * N * 4), o_tot = take(uint64_t(N) * 8), o_noff = take((uint64_t(N) + 1) * 8);
+  const size_t o_orow = take(cap_pairs * 4), o_ofil = take(cap_pairs * 4);
+  uint8_t* w = static_cast<uint8_t*>(ctx->pool->alloc(o));
+  if (!w) return 1;
+  auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(w + off); };
+  auto u64 = [&](size_t off) { return reinterpret_cast<uint64_t*>(w + off); };
+  out->ws = w;
+  out->row_routes = u32(o_rr);
+  out->node_off = u64(o_noff);
+  out->rows = u32(o_orow);
+  out->filters = u32(o_ofil);
+  out->total = u64(o_hoff) + cap;
+  auto fail = [&](int rc) {
+    hipStreamSynchronize(st);  // (a queued kernel may still write the workspace)
+    ctx->pool->release(w);
+    *out = DtSpec{};
+    return rc;
+  };
+#define FW_Q(expr)                                                                    \
+  do {                                                                                \
+    if ((expr) != hipSuccess) return fail(set_err(ctx, EMQX_GM_EDEVICE, "publish_window: " #expr)); \
+  } while (0)
+  FW_Q(hipMemsetAsync(u32(o_hnode), 0xFF, cap_pairs * 4, st));
+  hipLaunchKernelGGL(k_fw_row_routes, dim3(blocks_of(n)), dim3(256), 0, st, dt->dv, d_ro, n, d_ids, cap,
+                     out->row_routes);
+  FW_Q(hipGetLastError());
+  hipLaunchKernelGGL(k_fw_count, dim3(blocks_of(cap)), dim3(256), 0, st, dt->dv, d_ids, cap, d_ro + n, skip_node,
+                     u64(o_cnt));
+  FW_Q(hipGetLastError());
+  if (const int rc = scan_lengths(ctx, u64(o_cnt), cap, u64(o_hoff))) return fail(rc);
+  hipLaunchKernelGGL(k_fw_expand, dim3(blocks_of(cap)), dim3(256), 0, st, dt->dv, d_ro, n, d_ids, cap, u64(o_hoff),
+                     cap_pairs, skip_node, u32(o_hrow), u32(o_hfil), u32(o_hnode));
+  FW_Q(hipGetLastError());
+  uint32_t bits = 0;
+  while ((1u << bits) < N) ++bits;
+  const size_t lds = size_t(N) * 4;
+  hipLaunchKernelGGL(k_fw_hist, dim3(C), dim3(FW_BLOCK), lds, st, u32(o_hnode), cap_pairs, L, N, u32(o_hist));
+  FW_Q(hipGetLastError());
+  hipLaunchKernelGGL(k_fw_column, dim3(blocks_of(N)), dim3(256), 0, st, u32(o_hist), C, N, u64(o_tot));
+  FW_Q(hipGetLastError());
+  if (const int rc = scan_lengths(ctx, u64(o_tot), N, out->node_off)) return fail(rc);
+  hipLaunchKernelGGL(k_fw_scatter, dim3(C), dim3(FW_BLOCK), lds, st, u32(o_hrow), u32(o_hfil), u32(o_hnode), cap_pairs,
+                     L, N, bits, u32(o_hist), out->node_off, out->rows, out->filters);
+  FW_Q(hipGetLastError());
+#undef FW_Q
+  return 0;
 }
 
 }  // namespace gm
@@ -430,7 +518,7 @@ int emqx_gm_forward_plan_chunked(emqx_gm_ctx* ctx, emqx_gm_dests* dt, const emqx
   std::string why;
   if (const int rc = gm::dt_check_rows(dt, m, &why)) return gm::set_err(ctx, rc, "forward_plan: " + why);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  return gm::dt_plan_device(ctx, dt, m, skip_node, n_chunks, out);
+  return gm::dt_plan_device(ctx, dt, m, skip_node, n_chunks, out, false, nullptr);
   GM_GUARD_END(ctx)
 }
 

@@ -808,7 +808,7 @@ constexpr uint64_t kFanSmallDeliveries = uint64_t(16) << 20;
 uint64_t host_chunk_topics() { return std::max<uint64_t>(1024, env_u64("GM_HOST_CHUNK", 256u << 10)); }
 
 int run_host_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to, uint64_t n,
-                   uint32_t flags, emqx_gm_csr* out, emqx_gm_match_stats* st_out, SmallFan* fan) {
+                   uint32_t flags, emqx_gm_csr* out, emqx_gm_match_stats* st_out, SmallFan* fan, SmallSide* side) {
   // ---- outside the lock: the offsets checked, the call's inputs staged in a
   // page-locked buffer of its own: [text | 64 B of padding | u16 lengths (u32
   // offsets past 65,535 B)] -- past kMappedMax of text already page-locked, the
@@ -898,7 +898,7 @@ int run_host_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb
     drop_fan();
   };
   MatchTail tail;
-  tail.enqueue = [&](const uint64_t* d_ro, const uint32_t* d_ids, uint64_t cap) -> int {
+  auto rows_and_fan = [&](const uint64_t* d_ro, const uint32_t* d_ids, uint64_t cap) -> int {
     r_off = static_cast<uint64_t*>(ctx->hpool->alloc(obytes, true));
     size_t ib = 4096;  // (a power of two: the result buffers come back from the host pool's cache)
     while (ib < cap * 4 + 16) ib <<= 1;
@@ -950,6 +950,11 @@ int run_host_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb
     }
     ctx->pool->release_after(fd, 3, st);
     return 0;
+  };
+  tail.enqueue = [&](const uint64_t* d_ro, const uint32_t* d_ids, uint64_t cap) -> int {
+    const int qrc = rows_and_fan(d_ro, d_ids, cap);
+    if (!qrc && side) side->queue(d_ro, d_ids, cap);  // (the caller's stage: behind the rows and the fan-out)
+    return qrc;
   };
   void* ticket = nullptr;
   int rc = match_submit(ctx, idx, d_b, d_o, n, flags | EMQX_GM_DEVICE_IO | EMQX_GM_NO_TIMING, &ticket, &tail);
@@ -1003,6 +1008,20 @@ int run_host_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb
       fan->out.priv = ctx;
     } else {
       drop_fan();
+    }
+  }
+  if (side) {  // the caller's stage made whole, the true rows still on the device
+    dc.n_rows = n;
+    dc.on_device = 1;
+    if (const int src = side->finish(tail.used, &dc)) {
+      if (fan) {
+        fan->ok = false;
+        fan->out = emqx_gm_csr{};
+      }
+      drop_res();
+      ctx->pool->release(dc.row_off);
+      ctx->pool->release(dc.ids);
+      return src;
     }
   }
   ctx->pool->release(dc.row_off);

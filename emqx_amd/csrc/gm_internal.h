@@ -196,6 +196,8 @@ struct emqx_gm_ctx {
   std::vector<void*> pin_free, pin_all;
   double ids_per_topic = 4.0;  // speculative ids capacity of a match call (run_match), from recent calls
   double subs_per_match = 16.0;  // speculative deliveries capacity of a small host fan-out, from recent calls
+  // speculative pick / plan capacities of a publish window (gm_publish.hip), from recent windows
+  double hits_per_match = 1.0, pairs_per_match = 1.0;
   // A ring of 64-B pass-counter blocks (gm_match.hip MatchCall): a call takes
   // the next block, already zeroed -- the previous call's assembly kernel zeroes
   // it -- so a call needs no zeroing launch of its own.  State per block: 0 ready
@@ -589,8 +591,20 @@ struct SmallFan {
   bool queued = false, rows_spec = false;
   uint64_t total = 0, cap = 0;
 };
+// side (optional, emqx_gm_publish_window): a stage of the caller's behind the
+// speculative rows and fan-out, in the same round trip.  queue(row_off, ids,
+// cap) runs under ctx->mu before the call's one wait, with the device rows and
+// their ids capacity; it keeps its own failures (it then queued nothing).
+// finish(rows_spec, rows) runs under ctx->mu after the wait, while the call's
+// true device rows are still held: rows_spec says whether they are the ones
+// queue() saw.  A finish() that fails fails the call, which then returns nothing.
+struct SmallSide {
+  std::function<void(const uint64_t* row_off, const uint32_t* ids, uint64_t cap)> queue;
+  std::function<int(bool rows_spec, const emqx_gm_csr* rows)> finish;
+};
 int run_host_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to, uint64_t n,
-                   uint32_t flags, emqx_gm_csr* out, emqx_gm_match_stats* st_out, SmallFan* fan = nullptr);
+                   uint32_t flags, emqx_gm_csr* out, emqx_gm_match_stats* st_out, SmallFan* fan = nullptr,
+                   SmallSide* side = nullptr);
 int queue_fanout_spec(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint64_t* d_ro, const uint32_t* d_ids,
                       uint64_t n, uint64_t cap_m, uint64_t cap_f, uint64_t* seg_dst, uint64_t* row_off, uint32_t* ids);
 // A host-row fan-out of a publish window, the same way (entered WITHOUT

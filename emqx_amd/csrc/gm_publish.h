@@ -1,0 +1,26 @@
+// gm_publish.h — emqx_gm_publish_window's stage (gm_publish.hip), called by the
+// entry point (gm_api.cpp) once every argument is checked.
+#pragma once
+
+#include "gm_internal.h"
+
+namespace gm {
+
+struct PwArgs {
+  emqx_gm_shared* sh = nullptr;  // nullptr: no picks
+  uint32_t strategy = 0, seed = 0;
+  const uint32_t* msg_hash = nullptr;  // host, one per topic (EMQX_GM_SHARE_HASH)
+  emqx_gm_dests* dt = nullptr;   // nullptr: no plan
+  uint32_t skip_node = 0;
+};
+
+// A window run_host_small serves, whole on ctx's device (entered WITHOUT
+// ctx->mu): the match, its fan-out (fan, as run_host_small's), the picks and the
+// plan in one device round trip where the speculation holds.  res->deliveries
+// is left to the caller (fan->ok: fan->out).  On an error nothing is held and
+// the shared table's state is unchanged.
+int run_publish_window(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to, uint64_t n,
+                       uint32_t flags, const PwArgs& a, emqx_gm_publish_result* res, emqx_gm_publish_stats* st_out,
+                       emqx_gm_match_stats* mst, SmallFan* fan);
+
+}  // namespace gm

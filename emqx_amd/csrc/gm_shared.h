@@ -112,7 +112,26 @@ int sh_pick_host(emqx_gm_shared* sh, const emqx_gm_csr* m, uint32_t strategy, co
 int sh_upload(emqx_gm_ctx* ctx, emqx_gm_shared* sh);
 void sh_free_device(emqx_gm_shared* sh);
 int sh_read_state(emqx_gm_ctx* ctx, const emqx_gm_shared* sh, std::vector<uint32_t>& rr, std::vector<uint32_t>& st);
+// host_out: device rows in, but msg_hash and the result on the host (a publish
+// window's rerun); waits (optional): += the host-blocking device waits made
 int sh_pick_device(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, uint32_t strategy,
                    const uint32_t* msg_hash, uint32_t seed, uint32_t n_chunks, emqx_gm_csr* out_members,
-                   emqx_gm_csr* out_slots);
+                   emqx_gm_csr* out_slots, bool host_out = false, uint32_t* waits = nullptr);
+// A pick queued over a small call's speculative rows (emqx_gm_publish_window):
+// device pointers into one workspace `ws` of the context's pool, which the
+// caller releases behind the stream; *total is the true hit count.
+struct ShSpec {
+  void* ws = nullptr;
+  uint64_t* row_off = nullptr;  // [n + 1]
+  uint32_t* slots = nullptr;    // [cap_hits]
+  uint32_t* members = nullptr;  // [cap_hits]
+  const uint64_t* total = nullptr;
+  uint32_t* sh_rr = nullptr;    // round robin: the shadow of rr[] (SH_UNSET: untouched)
+  uint32_t* sh_st = nullptr;    // sticky: the shadow of st[]
+};
+int sh_queue_spec(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const uint64_t* d_ro, const uint32_t* d_ids, uint64_t n,
+                  uint64_t cap, uint64_t cap_hits, uint32_t strategy, const uint32_t* d_hash, uint32_t seed,
+                  ShSpec* out);
+// the shadow state written into the table (queued, no wait; under sh->mu)
+int sh_queue_commit(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const ShSpec& run);
 }  // namespace gm

@@ -29,10 +29,16 @@
 namespace gm {
 namespace {
 
+// nnz_p (optional, speculative rows: nnz is their capacity): the rows' own count
+// on the device; an entry past it counts 0 (the buffer holds stale words there)
 __global__ __launch_bounds__(256) void k_sh_count(ShView v, const uint32_t* __restrict__ ids, uint64_t nnz,
-                                                  uint64_t* __restrict__ cnt) {
+                                                  const uint64_t* __restrict__ nnz_p, uint64_t* __restrict__ cnt) {
   const uint64_t j = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (j >= nnz) return;
+  if (nnz_p && j >= *nnz_p) {
+    cnt[j] = 0;
+    return;
+  }
   const uint32_t f = ids[j];
   cnt[j] = f < v.n_filters ? v.sh_off[f + 1] - v.sh_off[f] : 0;  // (an id past the snapshot is skipped)
 }
@@ -54,14 +60,15 @@ __global__ __launch_bounds__(256) void k_sh_expand(ShView v, const uint64_t* __r
                                                    const uint64_t* __restrict__ hoff, uint64_t hits, uint32_t strategy,
                                                    const uint32_t* __restrict__ msg_hash, uint32_t seed,
                                                    uint32_t* __restrict__ out_slots,
-                                                   uint32_t* __restrict__ out_members) {
+                                                   uint32_t* __restrict__ out_members,
+                                                   uint32_t* st_out) {
   const uint64_t j = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (j >= nnz) return;
   const uint32_t f = ids[j];
   if (f >= v.n_filters) return;
   const uint32_t s0 = v.sh_off[f], s1 = v.sh_off[f + 1];
-  if (s0 == s1) return;
   uint64_t h = hoff[j];
+  if (s0 == s1 || hoff[j + 1] == h) return;  // (no hit counted: no slot, or an entry past speculative rows' count)
   uint64_t row = 0;
   if (strategy == EMQX_GM_SHARE_HASH || strategy == EMQX_GM_SHARE_RANDOM) {
     // the row of matched id j: the last r < n_rows with m_ro[r] <= j
@@ -82,7 +89,7 @@ __global__ __launch_bounds__(256) void k_sh_expand(ShView v, const uint64_t* __r
       got = v.st[s];
       if (got == SH_UNSET) {  // every hit of the slot computes the same value: identical plain stores
         got = v.mem_ids[m0 + (count == 1 ? 0 : sh_mix(seed, s) % count)];
-        v.st[s] = got;
+        st_out[s] = got;  // (the table's st, or a speculative window's shadow of it)
       }
     } else if (count == 1) {
       got = v.mem_ids[m0];
@@ -107,8 +114,9 @@ __global__ __launch_bounds__(256) void k_sh_hist(const uint32_t* __restrict__ sl
 // One lane per slot (coalesced across slots): hist[c][s] becomes the member
 // index the chunk's first hit on s takes, (first + hits of s in chunks < c) rem
 // Count, and rr[s] the index of the call's last hit on s.
+// rr_out: the table's rr, or a speculative window's shadow of it.
 __global__ __launch_bounds__(256) void k_sh_column(ShView v, uint32_t* __restrict__ hist, uint32_t n_chunks,
-                                                   uint32_t seed) {
+                                                   uint32_t seed, uint32_t* rr_out) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= v.n_slots) return;
   const uint32_t count = v.mem_off[s + 1] - v.mem_off[s];
@@ -125,7 +133,18 @@ __global__ __launch_bounds__(256) void k_sh_column(ShView v, uint32_t* __restric
     if (count > 1) next = (next + t) % count;
   }
   // next is the index after the last hit; a slot of one member reads and writes no state
-  if (any && count > 1) v.rr[s] = uint32_t((next + count - 1) % count);
+  if (any && count > 1) rr_out[s] = uint32_t((next + count - 1) % count);
+}
+
+// A speculative window's state made the table's (gm_publish.hip): the slots its
+// shadow arrays hold a value for, one lane per slot.
+__global__ __launch_bounds__(256) void k_sh_commit(uint32_t* __restrict__ rr, const uint32_t* __restrict__ sh_rr,
+                                                   uint32_t* __restrict__ st, const uint32_t* __restrict__ sh_st,
+                                                   uint32_t n_slots) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_slots) return;
+  if (sh_rr && sh_rr[s] != SH_UNSET) rr[s] = sh_rr[s];
+  if (sh_st && sh_st[s] != SH_UNSET) st[s] = sh_st[s];
 }
 
 __global__ __launch_bounds__(64) void k_sh_rank(ShView v, const uint32_t* __restrict__ slots, uint64_t hits,
@@ -212,10 +231,14 @@ int sh_read_state(emqx_gm_ctx* ctx, const emqx_gm_shared* sh, std::vector<uint32
 
 int sh_pick_device(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, uint32_t strategy,
                    const uint32_t* msg_hash, uint32_t seed, uint32_t n_chunks, emqx_gm_csr* out_members,
-                   emqx_gm_csr* out_slots) {
+                   emqx_gm_csr* out_slots, bool host_out, uint32_t* waits) {
   GM_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const bool dev = m->on_device != 0;
+  // (host_out: device rows, but host hashes and a host result -- a publish window's rerun, gm_publish.hip)
+  const bool dev_in = m->on_device != 0, dev = dev_in && !host_out;
+  auto waited = [&]() {
+    if (waits) ++*waits;
+  };
   const uint64_t n = m->n_rows, nnz = m->nnz;
   emqx_gm_csr* outs[2] = {out_members, out_slots};
   struct Undo {  // a failing call hands back no buffers
@@ -249,7 +272,10 @@ int sh_pick_device(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, u
       if (dev) GM_HIP(ctx, hipMemsetAsync(o->row_off, 0, (n + 1) * 8, st));
       else std::fill(o->row_off, o->row_off + n + 1, uint64_t(0));
     }
-    if (dev) GM_HIP(ctx, hipStreamSynchronize(st));
+    if (dev) {
+      GM_HIP(ctx, hipStreamSynchronize(st));
+      waited();
+    }
     undo.armed = false;
     return EMQX_GM_OK;
   }
@@ -259,17 +285,21 @@ int sh_pick_device(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, u
   const uint32_t* d_mids = m->ids;
   const uint32_t* d_hash = msg_hash;
   const bool need_hash = strategy == EMQX_GM_SHARE_HASH;
-  if (!dev) {
+  if (!dev_in) {
     b_ro = PoolBuf(ctx->pool, (n + 1) * 8);
     b_ids = PoolBuf(ctx->pool, nnz * 4);
-    if (need_hash) b_hash = PoolBuf(ctx->pool, n * 4);
-    if (!b_ro.p || !b_ids.p || (need_hash && !b_hash.p))
-      return set_err(ctx, EMQX_GM_ENOMEM, "shared_pick: device buffers");
+    if (!b_ro.p || !b_ids.p) return set_err(ctx, EMQX_GM_ENOMEM, "shared_pick: device buffers");
     GM_HIP(ctx, hipMemcpyAsync(b_ro.p, m->row_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
     GM_HIP(ctx, hipMemcpyAsync(b_ids.p, m->ids, nnz * 4, hipMemcpyHostToDevice, st));
-    if (need_hash) GM_HIP(ctx, hipMemcpyAsync(b_hash.p, msg_hash, n * 4, hipMemcpyHostToDevice, st));
     d_mro = b_ro.as<uint64_t>();
     d_mids = b_ids.as<uint32_t>();
+  }
+  if (!dev) {
+    if (need_hash) {
+      b_hash = PoolBuf(ctx->pool, n * 4);
+      if (!b_hash.p) return set_err(ctx, EMQX_GM_ENOMEM, "shared_pick: device buffers");
+      GM_HIP(ctx, hipMemcpyAsync(b_hash.p, msg_hash, n * 4, hipMemcpyHostToDevice, st));
+    }
     d_hash = need_hash ? b_hash.as<uint32_t>() : nullptr;
   }
   PoolBuf d_cnt(ctx->pool, nnz * 8), d_hoff(ctx->pool, (nnz + 1) * 8), d_ro;
@@ -279,7 +309,8 @@ int sh_pick_device(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, u
   if (const int rc = ev.create(ctx)) return rc;
   GM_HIP(ctx, hipEventRecord(ev.e[0], st));
   // enumerate
-  hipLaunchKernelGGL(k_sh_count, dim3(blocks_of(nnz)), dim3(256), 0, st, sh->dv, d_mids, nnz, d_cnt.as<uint64_t>());
+  hipLaunchKernelGGL(k_sh_count, dim3(blocks_of(nnz)), dim3(256), 0, st, sh->dv, d_mids, nnz,
+                     static_cast<const uint64_t*>(nullptr), d_cnt.as<uint64_t>());
   GM_HIP(ctx, hipGetLastError());
   if (const int rc = scan_lengths(ctx, d_cnt.as<uint64_t>(), nnz, d_hoff.as<uint64_t>())) return rc;
   uint64_t* ro_a = dev ? out_members->row_off : d_ro.as<uint64_t>();
@@ -292,6 +323,7 @@ int sh_pick_device(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, u
   GM_HIP(ctx, hipMemcpyAsync(&hits, d_hoff.as<uint64_t>() + nnz, 8, hipMemcpyDeviceToHost, st));
   if (!dev) GM_HIP(ctx, hipMemcpyAsync(out_members->row_off, d_ro.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
   GM_HIP(ctx, hipStreamSynchronize(st));
+  waited();
   if (!dev) std::copy(out_members->row_off, out_members->row_off + n + 1, out_slots->row_off);
   if (hits >= 0xFFFFFFFFull) return set_err(ctx, EMQX_GM_EOVERFLOW, "shared_pick: 2^32 - 1 hits or more in one call");
   out_members->nnz = out_slots->nnz = hits;
@@ -331,7 +363,7 @@ int sh_pick_device(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, u
     return set_err(ctx, EMQX_GM_ENOMEM, "shared_pick: result ids");
   // expand (and pick, but for round robin)
   hipLaunchKernelGGL(k_sh_expand, dim3(blocks_of(nnz)), dim3(256), 0, st, sh->dv, d_mro, n, d_mids, nnz,
-                     d_hoff.as<uint64_t>(), hits, strategy, d_hash, seed, o_slot, o_mem);
+                     d_hoff.as<uint64_t>(), hits, strategy, d_hash, seed, o_slot, o_mem, sh->dv.st);
   GM_HIP(ctx, hipGetLastError());
   GM_HIP(ctx, hipEventRecord(ev.e[2], st));
   if (strategy == EMQX_GM_SHARE_ROUND_ROBIN) {
@@ -339,7 +371,8 @@ int sh_pick_device(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, u
     hipLaunchKernelGGL(k_sh_hist, dim3(blocks_of(hits)), dim3(256), 0, st, o_slot, hits, L, uint32_t(S),
                        d_hist.as<uint32_t>());
     GM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_sh_column, dim3(blocks_of(S)), dim3(256), 0, st, sh->dv, d_hist.as<uint32_t>(), C, seed);
+    hipLaunchKernelGGL(k_sh_column, dim3(blocks_of(S)), dim3(256), 0, st, sh->dv, d_hist.as<uint32_t>(), C, seed,
+                       sh->dv.rr);
     GM_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_sh_rank, dim3(C), dim3(64), 0, st, sh->dv, o_slot, hits, L, d_hist.as<uint32_t>(), o_mem);
     GM_HIP(ctx, hipGetLastError());
@@ -351,16 +384,111 @@ int sh_pick_device(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, u
   }
   GM_HIP(ctx, hipEventRecord(ev.e[4], st));
   GM_HIP(ctx, hipStreamSynchronize(st));
-  for (int k = 0; k < 3; ++k) {
+  waited();
+  // (a publish window's rerun of a stateless strategy does not hold sh->mu, which guards last_ms)
+  for (int k = 0; k < 3 && !host_out; ++k) {
     float ms = 0;
     GM_HIP(ctx, hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
     sh->last_ms[k] = ms;
   }
-  float ms = 0;
-  GM_HIP(ctx, hipEventElapsedTime(&ms, ev.e[0], ev.e[4]));
-  sh->last_ms[3] = ms;
+  if (!host_out) {
+    float ms = 0;
+    GM_HIP(ctx, hipEventElapsedTime(&ms, ev.e[0], ev.e[4]));
+    sh->last_ms[3] = ms;
+  }
   undo.armed = false;
   return EMQX_GM_OK;
+}
+
+
+// The pick of a small call's SPECULATIVE rows (gm_publish.hip), queued on the
+// context stream with no wait and no read-back: the counts run over the ids'
+// capacity `cap` with the rows' own count read on the device (d_ro + n), the
+// expansion into cap_hits entries (slots pre-filled SH_UNSET, so the round-robin
+// passes skip the unused ones; their chunking is fixed from cap_hits).  The
+// table's state is read but not written: the new round-robin index and the
+// first sticky pick go to shadow arrays (SH_UNSET: untouched) that
+// sh_queue_commit applies once the host knows the run holds.  1: not queued
+// (no room, or a workspace past the cap).
+int sh_queue_spec(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const uint64_t* d_ro, const uint32_t* d_ids, uint64_t n,
+                  uint64_t cap, uint64_t cap_hits, uint32_t strategy, const uint32_t* d_hash, uint32_t seed,
+                  ShSpec* out) {
+  hipStream_t st = ctx->stream;
+  const uint64_t S = sh->hv.n_slots;
+  if (!S || !cap || !cap_hits) return 1;  // (a table without slots: the exact call answers without device work)
+  const bool rr = strategy == EMQX_GM_SHARE_ROUND_ROBIN, sticky = strategy == EMQX_GM_SHARE_STICKY;
+  uint32_t C = 1;
+  uint64_t L = cap_hits;
+  if (rr) {
+    C = uint32_t(std::min<uint64_t>(sh_rr_chunks(cap_hits, S), cap_hits));
+    L = (cap_hits + C - 1) / C;
+    C = uint32_t((cap_hits + L - 1) / L);
+    if (uint64_t(C) * S * 4 > SH_RR_WS_CAP) return 1;
+  }
+  // one workspace: cnt | hoff | row offsets | slots | members | hist | shadow
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += align_up(std::max<size_t>(bytes, 16), 256);
+    return at;
+  };
+  const size_t o_cnt = take(cap * 8), o_hoff = take((cap + 1) * 8), o_ro = take((n + 1) * 8);
+  const size_t o_slot = take(cap_hits * 4), o_mem = take(cap_hits * 4);
+  const size_t o_hist = rr ? take(uint64_t(C) * S * 4) : 0, o_sh = rr || sticky ? take(S * 4) : 0;
+  uint8_t* w = static_cast<uint8_t*>(ctx->pool->alloc(o));
+  if (!w) return 1;
+  auto at = [&](size_t off) { return static_cast<void*>(w + off); };
+  uint64_t* cnt = static_cast<uint64_t*>(at(o_cnt));
+  uint64_t* hoff = static_cast<uint64_t*>(at(o_hoff));
+  out->ws = w;
+  out->row_off = static_cast<uint64_t*>(at(o_ro));
+  out->slots = static_cast<uint32_t*>(at(o_slot));
+  out->members = static_cast<uint32_t*>(at(o_mem));
+  out->total = hoff + cap;
+  out->sh_rr = rr ? static_cast<uint32_t*>(at(o_sh)) : nullptr;
+  out->sh_st = sticky ? static_cast<uint32_t*>(at(o_sh)) : nullptr;
+  auto fail = [&](int rc) {
+    hipStreamSynchronize(st);  // (a queued kernel may still write the workspace)
+    ctx->pool->release(w);
+    *out = ShSpec{};
+    return rc;
+  };
+#define SH_Q(expr)                                                                    \
+  do {                                                                                \
+    if ((expr) != hipSuccess) return fail(set_err(ctx, EMQX_GM_EDEVICE, "publish_window: " #expr)); \
+  } while (0)
+  SH_Q(hipMemsetAsync(out->slots, 0xFF, cap_hits * 4, st));
+  if (rr || sticky) SH_Q(hipMemsetAsync(at(o_sh), 0xFF, S * 4, st));
+  hipLaunchKernelGGL(k_sh_count, dim3(blocks_of(cap)), dim3(256), 0, st, sh->dv, d_ids, cap, d_ro + n, cnt);
+  SH_Q(hipGetLastError());
+  if (const int rc = scan_lengths(ctx, cnt, cap, hoff)) return fail(rc);
+  hipLaunchKernelGGL(k_sh_rowoff, dim3(blocks_of(n + 1)), dim3(256), 0, st, d_ro, n, cap, hoff, out->row_off,
+                     static_cast<uint64_t*>(nullptr));
+  SH_Q(hipGetLastError());
+  hipLaunchKernelGGL(k_sh_expand, dim3(blocks_of(cap)), dim3(256), 0, st, sh->dv, d_ro, n, d_ids, cap, hoff, cap_hits,
+                     strategy, d_hash, seed, out->slots, out->members, out->sh_st);
+  SH_Q(hipGetLastError());
+  if (rr) {
+    uint32_t* hist = static_cast<uint32_t*>(at(o_hist));
+    SH_Q(hipMemsetAsync(hist, 0, uint64_t(C) * S * 4, st));
+    hipLaunchKernelGGL(k_sh_hist, dim3(blocks_of(cap_hits)), dim3(256), 0, st, out->slots, cap_hits, L, uint32_t(S), hist);
+    SH_Q(hipGetLastError());
+    hipLaunchKernelGGL(k_sh_column, dim3(blocks_of(S)), dim3(256), 0, st, sh->dv, hist, C, seed, out->sh_rr);
+    SH_Q(hipGetLastError());
+    hipLaunchKernelGGL(k_sh_rank, dim3(C), dim3(64), 0, st, sh->dv, out->slots, cap_hits, L, hist, out->members);
+    SH_Q(hipGetLastError());
+  }
+#undef SH_Q
+  return 0;
+}
+
+int sh_queue_commit(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const ShSpec& run) {
+  const uint32_t S = sh->hv.n_slots;
+  if (!S || (!run.sh_rr && !run.sh_st)) return 0;
+  hipLaunchKernelGGL(k_sh_commit, dim3(blocks_of(S)), dim3(256), 0, ctx->stream, sh->dv.rr, run.sh_rr, sh->dv.st,
+                     run.sh_st, S);
+  GM_HIP(ctx, hipGetLastError());
+  return 0;
 }
 
 }  // namespace gm
@@ -434,7 +562,7 @@ int emqx_gm_shared_pick_chunked(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx
   if (const int rc = gm::sh_check_rows(sh, m, &why)) return gm::set_err(ctx, rc, "shared_pick: " + why);
   std::lock_guard<std::mutex> tl(sh->mu);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  return gm::sh_pick_device(ctx, sh, m, strategy, msg_hash, seed, n_chunks, out_members, out_slots);
+  return gm::sh_pick_device(ctx, sh, m, strategy, msg_hash, seed, n_chunks, out_members, out_slots, false, nullptr);
   GM_GUARD_END(ctx)
 }
 

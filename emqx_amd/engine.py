@@ -473,6 +473,51 @@ class Context:
             lib().emqx_gm_csr_free(self.h, C.byref(m))
             lib().emqx_gm_csr_free(self.h, C.byref(d))
 
+    def publish_window(self, index: Index, topics, exact: bool = True, shared=None, strategy="round_robin",
+                       hashes=None, seed: int = 0, dests=None, skip_node: Optional[int] = None):
+        """A whole publish window in one call (emqx_gm_publish_window): the match
+        and its fan-out as ``match_fanout``, the shared picks of ``shared`` (a
+        SharedTable) as ``shared.pick`` on the matched rows with ``(strategy,
+        hashes, seed)``, and the forward plan of ``dests`` (a DestTable) as
+        ``dests.plan`` on them with ``skip_node`` -- one device round trip where
+        the speculation holds.  Returns ``(matches, deliveries, picks, plan,
+        stats)``: ``picks`` is ``(row_off, members, slots)`` or None without
+        ``shared``, ``plan`` a ForwardPlan or None without ``dests``, ``stats``
+        the call's emqx_gm_publish_stats as a dict."""
+        from .cluster import _plan_to_numpy, _skip
+        from .shared import _strategy
+        tb, to = topics if isinstance(topics, tuple) else pack(topics)
+        n = len(to) - 1
+        hs = None if hashes is None else np.ascontiguousarray(hashes, np.uint32)
+        if hs is not None and len(hs) != n:
+            raise ValueError("one hash per topic")
+        if hs is not None and len(hs) == 0:
+            hs = np.zeros(1, np.uint32)
+        o = _lib.PublishOpts()
+        o.flags = _lib.WITH_EXACT if exact else 0
+        o.shared = shared.h if shared is not None else None
+        o.strategy = _strategy(strategy)
+        o.seed = seed & 0xFFFFFFFF
+        o.msg_hash = hs.ctypes.data if hs is not None else None
+        o.dests = dests.h if dests is not None else None
+        o.skip_node = _skip(skip_node)
+        res, st = _lib.PublishResult(), _lib.PublishStats()
+        check(lib().emqx_gm_publish_window(self.h, index.h, _ptr(tb), _ptr(to), n, C.byref(o), C.byref(res),
+                                           C.byref(st)), self.h, "publish_window")
+        try:
+            picks = plan = None
+            if shared is not None:
+                ro, mem = _csr_to_numpy(res.pick_members)
+                ro2, slots = _csr_to_numpy(res.pick_slots)
+                assert np.array_equal(ro, ro2)
+                picks = (ro, mem, slots)
+            if dests is not None:
+                plan = _plan_to_numpy(res.forwards)
+            stats = {name: int(getattr(st, name)) for name, _ in _lib.PublishStats._fields_}
+            return _csr_to_numpy(res.matches), _csr_to_numpy(res.deliveries), picks, plan, stats
+        finally:
+            lib().emqx_gm_publish_result_free(self.h, C.byref(res))
+
     def match_windows(self, index: Index, windows, exact: bool = True, fanout: bool = True):
         """Many publish windows in one call (emqx_gm_match_windows): ``windows`` is a
         sequence of topic lists (or packed ``(bytes, offsets)`` pairs).  Returns one

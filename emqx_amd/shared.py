@@ -259,10 +259,17 @@ class SharedSub:
         strategies.  ``seed`` defaults to a per-call value derived from the
         constructor's."""
         t = self.table(index)
+        auto = self.next_seed()
+        ro, mem, slots = t.pick(rows, strategy, hashes, auto if seed is None else seed)
+        return self.picks_rows(ro, mem, slots)
+
+    def next_seed(self) -> int:
+        """The per-call seed: counts the call and derives its seed from the constructor's."""
         self.calls += 1
-        if seed is None:
-            seed = (self.seed + self.calls * 0x9E3779B9) & 0xFFFFFFFF
-        ro, mem, slots = t.pick(rows, strategy, hashes, seed)
+        return (self.seed + self.calls * 0x9E3779B9) & 0xFFFFFFFF
+
+    def picks_rows(self, ro, mem, slots):
+        """A pick of the current table, per row: [(group, filter, picked subscriber)]."""
         out = []
         for r in range(len(ro) - 1):
             row = []

@@ -68,6 +68,8 @@
  *   host path:          GM_HOST_SIMPLE, GM_HOST_PIPE, GM_HOST_CHUNK,
  *     GM_HOST_THREADS, GM_HOST_BOUNCE, GM_HOST_WIDE_ROWS, GM_HOST_OFF32,
  *     GM_FANOUT_MULTI_MIN, GM_FANOUT_SIMPLE, GM_FANOUT_FUSED_ONLY;
+ *   publish window:     GM_PW_CAP_HITS, GM_PW_CAP_PAIRS (the speculative pick /
+ *     plan capacities as given; 0: that part is not speculated);
  *   updates:            GM_UPDATE_OVERLAY, GM_UPDATE_UNFUSED, GM_SPARE_BLOB_MIN;
  *   diagnostics:        GM_UPDATE_TIMING, GM_INDEX_STATS, GM_INDEX_VERIFY.
  */
@@ -781,6 +783,73 @@ int emqx_gm_forwards_free(emqx_gm_ctx *ctx, emqx_gm_forwards *fw);
 int emqx_gm_dests_info(const emqx_gm_dests *dt, emqx_gm_dests_info_t *info);
 /* drops the table and its reference on the snapshot */
 int emqx_gm_dests_release(emqx_gm_dests *dt);
+
+/* ---- a whole publish window in one device round trip (gm_publish.hip) ----
+ * A broker node's unit of work is a publish window, and for every message of
+ * it the node needs the matched route filters, their local subscribers, one
+ * member per matched shared group and the remote nodes to forward to
+ * (emqx_broker:publish/1 .. route/2, apps/emqx/src/emqx_broker.erl:204-215,
+ * 245-293; emqx_shared_sub:dispatch/3).  emqx_gm_publish_window computes all
+ * four in ONE call: the picks and the plan are queued on the device behind the
+ * match's speculative rows and fan-out, before the call's one host-blocking
+ * wait, and one kernel copies every side result to page-locked host memory.
+ * CONTRACT: the result is bit-equal to, on the same tables and in this order,
+ *   emqx_gm_match_fanout(topics, flags), emqx_gm_shared_pick on the returned
+ *   host rows with (strategy, msg_hash, seed), emqx_gm_forward_plan on the same
+ *   rows with skip_node -- every array, n_pairs, and the shared table's
+ *   round-robin / sticky state afterwards.
+ * Every array is a host pointer from the context's host pool; free the result
+ * with emqx_gm_publish_result_free, or each member on its own with
+ * emqx_gm_csr_free / emqx_gm_forwards_free.  With both tables NULL the call is
+ * emqx_gm_match_fanout.
+ * SPECULATION: the picks run into a capacity of hits, the plan into a capacity
+ * of pairs (this context's recent hits / pairs per match x 1.25, a power of
+ * two, at least 1024); the shared table's state is not written until the host
+ * has seen that the run holds (a small kernel then commits it, without a wait).
+ * What did not hold runs again at its exact size on the rows still in HBM:
+ * both side results when the rows were not the speculative ones, only the
+ * picks (the plan) when the hits (pairs) passed their capacity; deliveries
+ * past theirs follow emqx_gm_match_fanout's rule.  emqx_gm_publish_stats says
+ * which part came from the first round trip.
+ * A window emqx_gm_match_fanout would not serve in one round trip (more than
+ * one host chunk, an overlay or sharded snapshot, an index without subscriber
+ * lists) takes the three calls in sequence: correct, with more waits
+ * (device_waits is then 0: not counted).  On a multi-device context the window
+ * runs whole on the first listed device, which holds the side tables.
+ * ERRORS: a NULL argument, unknown flags, non-monotone offsets, a strategy past
+ * EMQX_GM_SHARE_RANDOM, EMQX_GM_SHARE_HASH without msg_hash, a table bound to a
+ * snapshot other than idx or living on another device: EMQX_GM_EINVAL (a
+ * host-only table: EMQX_GM_EUNSUPPORTED) before any device work, no output
+ * touched, no state changed.  On any later error every output is zeroed and
+ * nothing is held; the shared state is unchanged unless the error is the
+ * deliveries' rerun failing after the picks were committed.
+ * THREADS: windows with a stateful strategy (round robin, sticky) on one table
+ * are serialised from queueing to commit; hash and random windows overlap. */
+typedef struct {
+  uint32_t flags;            /* EMQX_GM_WITH_EXACT or 0, as emqx_gm_match_fanout           */
+  emqx_gm_shared *shared;    /* NULL: no picks                                             */
+  uint32_t strategy, seed;   /* as emqx_gm_shared_pick                                     */
+  const uint32_t *msg_hash;  /* host, n_topics entries; required for EMQX_GM_SHARE_HASH    */
+  emqx_gm_dests *dests;      /* NULL: no forward plan                                      */
+  uint32_t skip_node;        /* as emqx_gm_forward_plan                                    */
+  uint64_t reserved[2];
+} emqx_gm_publish_opts;
+typedef struct {
+  emqx_gm_csr matches, deliveries;      /* as emqx_gm_match_fanout                          */
+  emqx_gm_csr pick_members, pick_slots; /* as emqx_gm_shared_pick on host rows (zeroed without `shared`) */
+  emqx_gm_forwards forwards;            /* as emqx_gm_forward_plan on host rows (zeroed without `dests`) */
+} emqx_gm_publish_result;
+typedef struct {
+  uint32_t device_waits;   /* host-blocking waits on the device made by this call          */
+  uint8_t rows_spec, fanout_spec, picks_spec, forwards_spec; /* 1: that part came from the first round trip */
+  uint64_t n_hits, n_pairs;       /* shared hits, forward pairs                            */
+  uint64_t cap_hits, cap_pairs;   /* the speculative capacities used (0: not speculated)   */
+} emqx_gm_publish_stats;
+int emqx_gm_publish_window(emqx_gm_ctx *ctx, const emqx_gm_index *idx, const uint8_t *topic_bytes,
+                           const uint64_t *topic_off, uint64_t n_topics, const emqx_gm_publish_opts *opts,
+                           emqx_gm_publish_result *out, emqx_gm_publish_stats *stats /* may be NULL */);
+/* frees every member of a result and zeroes it */
+int emqx_gm_publish_result_free(emqx_gm_ctx *ctx, emqx_gm_publish_result *res);
 
 /* ---- authorization check (gm_authz.cpp / gm_authz.hip): the first matching ACL rule per request ----
  * Every PUBLISH and SUBSCRIBE passes emqx_authz:authorize/5 before the router;

@@ -14,6 +14,7 @@
          match_batch/2, match_routes_batch/2, fanout_batch/2, empty/1, export_index/1, import_index/1]).
 -export([load_retained/1, load_retained/2, match_retained/3, expire_retained/2]).
 -export([load_shared/3, load_shared/4, pick_shared/4, pick_shared_nif/5]).
+-export([publish_window/4, publish_window_nif/5]).
 -export([load_authz/1, authorize_batch/2, authz_rule/2, authz_request/3, authorize/5]).
 -export([match/2]).
 
@@ -160,6 +161,30 @@ pick_shared(Table, Msgs, Strategy, Seed) ->
 -spec pick_shared_nif(reference(), [binary()], 0..3, [non_neg_integer()], non_neg_integer()) ->
           [[{binary(), {non_neg_integer(), non_neg_integer()}}]] | {error, term()}.
 pick_shared_nif(_Table, _Topics, _Strategy, _Hashes, _Seed) -> erlang:nif_error(nif_not_loaded).
+
+%% A whole publish window in one device round trip (emqx_gm_publish_window): per
+%% message {Topic, ClientId}, in order, {what fanout_batch/2 gives for the topic,
+%% what pick_shared/4 gives for it} -- emqx_broker:publish/1's route + dispatch
+%% and emqx_shared_sub:dispatch/3's pick, where the three calls would make five
+%% waits on the device.  Table's snapshot must come from load_index/2.
+-spec publish_window(reference(), [{binary(), term()}], atom(), non_neg_integer()) ->
+          [{[{binary(), [non_neg_integer()]}], [{binary(), {non_neg_integer(), non_neg_integer()}}]}] |
+          {error, term()}.
+publish_window(Table, Msgs, Strategy, Seed) ->
+    Topics = [T || {T, _} <- Msgs],
+    {S, Hashes} = case Strategy of
+                      hash_topic -> {0, [erlang:phash2(T) || {T, _} <- Msgs]};
+                      H when H =:= hash; H =:= hash_clientid -> {0, [erlang:phash2(C) || {_, C} <- Msgs]};
+                      round_robin -> {1, []};
+                      sticky -> {2, []};
+                      random -> {3, []}
+                  end,
+    publish_window_nif(Table, Topics, S, Hashes, Seed band 16#FFFFFFFF).
+
+-spec publish_window_nif(reference(), [binary()], 0..3, [non_neg_integer()], non_neg_integer()) ->
+          [{[{binary(), [non_neg_integer()]}], [{binary(), {non_neg_integer(), non_neg_integer()}}]}] |
+          {error, term()}.
+publish_window_nif(_Table, _Topics, _Strategy, _Hashes, _Seed) -> erlang:nif_error(nif_not_loaded).
 
 %% The authorization chain (file and built-in-database sources, in order) as
 %% one table in HBM (emqx_gm_authz_build).  Segment = {Kind, [{Key, [Rule]}]}:

@@ -791,6 +791,99 @@ static ERL_NIF_TERM pick_shared_nif(ErlNifEnv *env, int argc, const ERL_NIF_TERM
   return result;
 }
 
+/* publish_window_nif(Table, [Topic], Strategy :: 0..3, [Hash], Seed) ->
+ *     [{[{Filter, [SubId]}], [{Filter, {GroupId, MemberId}}]}]
+ * per topic, in batch order, what fanout_batch/2 and pick_shared_nif/5 give for
+ * it -- the matched filters with their local subscribers, and the member picked
+ * for every {Group, Filter} the topic matches -- from ONE emqx_gm_publish_window:
+ * one device round trip for the window instead of the match, the fan-out and
+ * the pick one after the other.  The table's snapshot must come from
+ * load_index/2.  (The node destinations have no table in this shim yet, so the
+ * window carries no forward plan.) */
+static ERL_NIF_TERM publish_window_nif(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_shared_res *r;
+  uint8_t *tb;
+  uint64_t *to, n, i, k, d_pos;
+  unsigned strategy, seed, nh = 0, v;
+  uint32_t *hash = NULL;
+  emqx_gm_publish_opts o;
+  emqx_gm_publish_result w;
+  ERL_NIF_TERM result, *rows, h, t;
+  int rc, bad = 0;
+  (void)argc;
+  if (!enif_get_resource(env, argv[0], SHARED_RT, (void **)&r) || !enif_get_uint(env, argv[2], &strategy) ||
+      !enif_get_list_length(env, argv[3], &nh) || !enif_get_uint(env, argv[4], &seed))
+    return enif_make_badarg(env);
+  if (!pack_topics(env, argv[1], &tb, &to, &n)) return enif_make_badarg(env);
+  if (strategy == EMQX_GM_SHARE_HASH) {
+    if (nh != n) {
+      free_topics(tb, to);
+      return enif_make_badarg(env);
+    }
+    hash = enif_alloc(sizeof(uint32_t) * (n ? n : 1));
+    t = argv[3];
+    i = 0;
+    while (enif_get_list_cell(env, t, &h, &t)) {
+      if (!enif_get_uint(env, h, &v)) {
+        enif_free(hash);
+        free_topics(tb, to);
+        return enif_make_badarg(env);
+      }
+      hash[i++] = v;
+    }
+  }
+  memset(&o, 0, sizeof(o));
+  o.flags = EMQX_GM_WITH_EXACT;
+  o.shared = r->sh;
+  o.strategy = strategy;
+  o.seed = seed;
+  o.msg_hash = hash;
+  rc = emqx_gm_publish_window(CTX, r->idx, tb, to, n, &o, &w, NULL);
+  free_topics(tb, to);
+  if (hash) enif_free(hash);
+  if (rc != EMQX_GM_OK) return error_tuple(env, rc);
+  rows = enif_alloc(sizeof(ERL_NIF_TERM) * (n ? n : 1));
+  for (i = 0; i < n && !bad; ++i) {
+    ERL_NIF_TERM fan = enif_make_list(env, 0), picks = enif_make_list(env, 0);
+    d_pos = w.deliveries.row_off[i + 1];
+    for (k = w.matches.row_off[i + 1]; k > w.matches.row_off[i] && !bad; --k) { /* filters back to front */
+      const uint8_t *p;
+      uint64_t l, c, j;
+      ERL_NIF_TERM subs = enif_make_list(env, 0);
+      const uint32_t f = w.matches.ids[k - 1];
+      if (emqx_gm_index_filter(r->idx, f, &p, &l) != EMQX_GM_OK ||
+          emqx_gm_index_subscriber_count(r->idx, f, &c) != EMQX_GM_OK || c > d_pos - w.deliveries.row_off[i]) {
+        bad = 1;
+        break;
+      }
+      for (j = 0; j < c; ++j)
+        subs = enif_make_list_cell(env, enif_make_uint(env, w.deliveries.ids[d_pos - 1 - j]), subs);
+      d_pos -= c;
+      fan = enif_make_list_cell(env, enif_make_tuple2(env, enif_make_resource_binary(env, r, p, l), subs), fan);
+    }
+    for (k = w.pick_members.row_off[i + 1]; k > w.pick_members.row_off[i] && !bad; --k) {
+      const uint8_t *p = NULL;
+      uint64_t l = 0;
+      uint32_t f = 0, g = 0;
+      if (emqx_gm_shared_slot(r->sh, w.pick_slots.ids[k - 1], &f, &g, NULL, NULL) != EMQX_GM_OK ||
+          emqx_gm_index_filter(r->idx, f, &p, &l) != EMQX_GM_OK) {
+        bad = 1;
+        break;
+      }
+      picks = enif_make_list_cell(
+          env,
+          enif_make_tuple2(env, enif_make_resource_binary(env, r, p, l),
+                           enif_make_tuple2(env, enif_make_uint(env, g), enif_make_uint(env, w.pick_members.ids[k - 1]))),
+          picks);
+    }
+    rows[i] = enif_make_tuple2(env, fan, picks);
+  }
+  result = bad ? error_tuple(env, EMQX_GM_EINVAL) : enif_make_list_from_array(env, rows, (unsigned)n);
+  enif_free(rows);
+  emqx_gm_publish_result_free(CTX, &w);
+  return result;
+}
+
 /* ---- authorization check (emqx_gm_authz_*): emqx_authz:do_authorize/4 over file + built-in-database sources ----
  * Growable arrays for the flat description / request batch. */
 typedef struct {
@@ -1057,6 +1150,7 @@ static ErlNifFunc funcs[] = {
     {"load_shared", 3, load_shared, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"load_shared", 4, load_shared, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"pick_shared_nif", 5, pick_shared_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"publish_window_nif", 5, publish_window_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"load_authz", 1, load_authz, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"authorize_batch", 2, authorize_batch, ERL_NIF_DIRTY_JOB_CPU_BOUND},
 };
