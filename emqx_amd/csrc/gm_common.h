@@ -1,5 +1,5 @@
 // gm_common.h — index layout in HBM and the word hash shared by the host index
-// compiler (gm_index.cpp) and the HIP kernels (gm_match.hip).
+// compiler (gm_index.cpp) and the HIP kernels (gm_match.hip, gm_csr.hip, gm_update.hip).
 //
 // The flat index replaces the reference's ETS ordered_set of {Key, 0|1} keys
 // (apps/emqx/src/emqx_trie.erl:52-58) with a level trie:

@@ -1,6 +1,6 @@
 // gm_gather.h — one contiguous output range from n variable-length segments
 // (the prefix plan's topic permute, gm_route.hip, and its row un-permute,
-// gm_match.hip).  Segment i (SEG::at(i) = its first element and length in src)
+// gm_csr.hip).  Segment i (SEG::at(i) = its first element and length in src)
 // lands at dst + out_off[i]; out_off is the exclusive scan of the lengths.
 //
 // A block takes 256 consecutive segments = one contiguous output range.  Its

@@ -391,11 +391,52 @@ int match_submit(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, 
                  uint32_t flags, void** ticket, MatchTail* tail = nullptr);
 int match_wait(emqx_gm_ctx* ctx, void* ticket, emqx_gm_csr* out, MatchTail* tail = nullptr,
                emqx_gm_match_stats* st_out = nullptr);
+// write the root's '+' record (IndexView::d0_root) from view v's
+// depth-1 hot table on the device; d0 is the region's device address (v's own
+// pointer is const).  0: written (the caller sets IX_D0), 1: not wanted
+// (GM_D0=0), <0: error.
+int refresh_d0(emqx_gm_ctx* ctx, const IndexView& v, void* d0);
+// a call's device rows handed out as its result (device_out: the pool buffers
+// themselves; else copied into host buffers of the context's pool), and the
+// time between two events (0 when either was not recorded); also used by gm_csr.hip
+int finish_csr(emqx_gm_ctx* ctx, uint64_t n, uint64_t nnz, PoolBuf& row_off, PoolBuf& ids, bool device_out,
+               emqx_gm_csr* out);
+float ev_ms(hipEvent_t a, hipEvent_t b);
+// gm_csr.hip: what consumes finished rows
 int run_fanout(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_csr* m, uint32_t flags,
                emqx_gm_csr* out, uint32_t part = 0, uint32_t n_parts = 1, uint64_t* first_out = nullptr);
+// the device work of a small host fan-out (gm_host.cpp run_fanout_small) and of
+// the fan-out behind a small host call's speculative rows (run_host_small), queued without a wait
+int queue_fanout_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint64_t* d_off, const uint32_t* d_ids,
+                       uint64_t n, uint64_t nnz, uint64_t total, uint64_t* seg_dst, uint64_t* row_off, uint32_t* ids);
+int queue_fanout_spec(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint64_t* d_ro, const uint32_t* d_ids,
+                      uint64_t n, uint64_t cap_m, uint64_t cap_f, uint64_t* seg_dst, uint64_t* row_off, uint32_t* ids);
+// Output elements per workgroup: from 1,024 (a publish window's ~100k
+// deliveries in ~100 workgroups, not 30: 63 -> ~20 us) up to 65,536 for large
+// fan-outs (C4: 0.94 -> 0.81 ms against 4,096, fewer per-block segment
+// searches), a multiple of 1,024 (4 per thread step).  Also used by
+// gm_update.hip (its segment copies cut their output the same way).
+inline uint64_t fan_per_block(uint64_t total) {
+  uint64_t per = total / 2048;  // ~8 workgroups per CU
+  per = per < 1024 ? 1024 : per > 65536 ? 65536 : per;
+  return (per + 1023) & ~uint64_t(1023);
+}
 int run_merge_rows(emqx_gm_ctx* ctx, uint64_t n_rows, uint64_t stride, uint32_t n_pieces, const uint32_t* d_lens,
                    const uint32_t* d_ids, uint32_t flags, emqx_gm_csr* out);
 int run_row_lengths(emqx_gm_ctx* ctx, const emqx_gm_csr* csr, uint32_t* d_out);
+int run_match_overlay(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to, uint64_t n,
+                      uint32_t flags, emqx_gm_csr* out);
+int unpermute_rows(emqx_gm_ctx* ctx, uint64_t n, const uint32_t* d_perm, const uint32_t* d_lens, const uint32_t* d_ids,
+                   uint32_t flags, emqx_gm_csr* out);
+int scan_lengths(emqx_gm_ctx* ctx, const uint64_t* len, uint64_t n, uint64_t* out);
+// the host path's u16 topic lengths -> u64 offsets (n + 1 entries, an exclusive scan) on stream st
+int scan_len16(emqx_gm_ctx* ctx, hipStream_t st, const uint16_t* len, uint64_t n, uint64_t* out);
+// offset conversions of the host-buffer path (n1 = entries)
+int launch_off32_to_64(hipStream_t st, const uint32_t* in, uint64_t n1, uint64_t* out);
+int launch_off64_to_32(hipStream_t st, const uint64_t* in, uint64_t n1, uint32_t* out);
+int launch_copy_u32x2(hipStream_t st, const uint32_t* s0, uint32_t* d0, uint64_t n0, const uint32_t* s1, uint32_t* d1,
+                      uint64_t n1, const uint64_t* n1_max = nullptr);
+int launch_add_u64(hipStream_t st, uint64_t* p, uint64_t n1, uint64_t add);
 // prefix sharding (gm_route.hip) and the exchange's device steps
 int route_plan(const uint8_t* fb, const uint64_t* fo, uint64_t n, uint32_t n_shards, uint32_t* shard_out,
                emqx_gm_route** out);
@@ -413,9 +454,6 @@ int route_filter_shards_host(const emqx_gm_route* r, const uint8_t* fb, const ui
                              uint32_t* shard_out);
 int permute_topics(emqx_gm_ctx* ctx, const uint8_t* d_tb, const uint64_t* d_to, uint64_t n, const uint32_t* d_perm,
                    uint8_t* d_out, uint64_t* d_out_off);
-int unpermute_rows(emqx_gm_ctx* ctx, uint64_t n, const uint32_t* d_perm, const uint32_t* d_lens, const uint32_t* d_ids,
-                   uint32_t flags, emqx_gm_csr* out);
-int scan_lengths(emqx_gm_ctx* ctx, const uint64_t* len, uint64_t n, uint64_t* out);
 
 // A replica an update makes on member context m from prev's replica `prev`
 // (gm_overlay.cpp patch_update, gm_subs.cpp update_subs): each member applies
@@ -463,6 +501,8 @@ int patch_update(emqx_gm_ctx* ctx, emqx_gm_index* prev, const std::set<uint32_t>
                  const std::set<std::string>& dset, emqx_gm_index** out, std::vector<uint32_t>* rmap_out = nullptr,
                  bool trie_only = false, std::vector<RepTarget>* reps = nullptr, const GmapShift* gs = nullptr);
 bool well_formed_filter(const uint8_t* p, uint64_t len);
+int overlay_filter(const emqx_gm_index* idx, uint32_t id, const uint8_t** bytes, uint64_t* len);
+void free_overlay(emqx_gm_index* idx);
 // gm_image.cpp: index images (emqx_gm_index_export / _import) and the lazy host mirror
 int index_export(emqx_gm_ctx* ctx, const emqx_gm_index* idx, uint32_t flags, uint8_t* buf, uint64_t* size);
 int index_import(emqx_gm_ctx* ctx, const uint8_t* img, uint64_t size, const void* d_blob, emqx_gm_index** out);
@@ -480,11 +520,6 @@ uint64_t* image_field(uint8_t* img, const std::string& name);
 uint32_t image_view_u32(uint8_t* img, int which, int t);
 void image_view_set_u32(uint8_t* img, int which, int t, uint32_t x);
 void image_reseal(uint8_t* img, uint64_t size);
-// gm_match.hip: write the root's '+' record (IndexView::d0_root) from view v's
-// depth-1 hot table on the device; d0 is the region's device address (v's own
-// pointer is const).  0: written (the caller sets IX_D0), 1: not wanted
-// (GM_D0=0), <0: error.
-int refresh_d0(emqx_gm_ctx* ctx, const IndexView& v, void* d0);
 // a plain index's host mirror is kept from the build when its tables are at most this big
 // (C3's 4.6 GB tables keep theirs: a lazy first update downloads the tables,
 // 0.8 s at C3 over pageable copies; the 38 GB C5 index does not)
@@ -495,28 +530,27 @@ uint64_t filter_rank(const emqx_gm_index* idx, const uint8_t* f, uint64_t len, b
 int update_subs(emqx_gm_ctx* ctx, emqx_gm_index* prev, const uint8_t* fb, const uint64_t* fo, const uint32_t* subs,
                 const uint8_t* ops, uint64_t n_ops, emqx_gm_index** out);
 bool is_pinned(const emqx_gm_index* idx, uint64_t f);
-// gm_match.hip: segments [src_off[j], src_off[j] + (dst_off[j+1] - dst_off[j])) of
+// gm_update.hip: the device side of in-place updates (to the next file heading)
+// segments [src_off[j], src_off[j] + (dst_off[j+1] - dst_off[j])) of
 // the device array src gathered into host `out` (dst_off[m] elements), one
 // device gather + one copy back
 int gather_segments(emqx_gm_ctx* ctx, const uint32_t* src, const std::vector<uint64_t>& src_off,
                     const std::vector<uint64_t>& dst_off, uint32_t* out);
-// gm_match.hip: the new subscriber CSR of a subscriber-only update_subs batch
+// the new subscriber CSR of a subscriber-only update_subs batch
 // (ids unchanged; O(delta) host work, see there)
 int shift_subs_device(emqx_gm_ctx* ctx, const emqx_gm_index* prev, emqx_gm_index* idx,
                       const std::vector<uint32_t>& aff_ids, const std::vector<uint64_t>& aff_off,
                       const std::vector<uint32_t>& aff_buf);
-// gm_match.hip: the new subscriber CSR of update_subs (see there)
+// the new subscriber CSR of update_subs (see there)
 int rebuild_subs_device(emqx_gm_ctx* ctx, const emqx_gm_index* prev, emqx_gm_index* idx,
                         const std::vector<uint64_t>& new_soff, const std::vector<uint32_t>& inv,
                         const std::vector<uint32_t>& aff_ids, const std::vector<uint64_t>& aff_off,
                         const std::vector<uint32_t>& aff_buf);
-int overlay_filter(const emqx_gm_index* idx, uint32_t id, const uint8_t** bytes, uint64_t* len);
-void free_overlay(emqx_gm_index* idx);
 // An op of Patcher::orops whose offset carries PATCH_AND clears its bits
 // instead of setting them (an op never sets a bit another op clears, so the
 // device applies them in any order).
 constexpr uint64_t PATCH_AND = 1ull << 63;
-// gm_match.hip: the device side of an in-place update (patch_update): dst =
+// the device side of an in-place update (patch_update): dst =
 // src (bytes), then the host-patched byte ranges (offset, length) of `host`
 // written over it, the OR / AND ops (offset of a word, bits) applied, then every
 // filter-id field of the hot slots and of nodes [0, n_nodes) renumbered by
@@ -544,7 +578,7 @@ struct GmapShift {
   const IdShift* G = nullptr;
   const std::vector<uint32_t>* add_gid = nullptr;
 };
-// gm_match.hip, k_gmap_shift: a shard's new local-to-global id map.  For every
+// k_gmap_shift: a shard's new local-to-global id map.  For every
 // old or temporary local id i < nb + add_gid.size(): j = L(i) (rmap on the
 // device, the shard's local shift; nullptr: the identity, no local change;
 // NONE: deleted), new_gmap[j] = G(old_gmap[i]) for i < nb, else add_gid[i - nb].
@@ -557,18 +591,8 @@ struct GmapJob {
 };
 // a shard without local changes: its new map alone (queued and waited for on ctx's stream)
 int shift_gmap_device(emqx_gm_ctx* ctx, const GmapJob& job);
-// gm_match.hip
-int run_match_overlay(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to, uint64_t n,
-                      uint32_t flags, emqx_gm_csr* out);
+// gm_api.cpp
 int set_err(emqx_gm_ctx* ctx, int code, const std::string& msg);
-// gm_match.hip: offset conversions of the host-buffer path (n1 = entries)
-int launch_off32_to_64(hipStream_t st, const uint32_t* in, uint64_t n1, uint64_t* out);
-int launch_off64_to_32(hipStream_t st, const uint64_t* in, uint64_t n1, uint32_t* out);
-int launch_copy_u32x2(hipStream_t st, const uint32_t* s0, uint32_t* d0, uint64_t n0, const uint32_t* s1, uint32_t* d1,
-                      uint64_t n1, const uint64_t* n1_max = nullptr);
-int launch_add_u64(hipStream_t st, uint64_t* p, uint64_t n1, uint64_t add);
-// the host path's u16 topic lengths -> u64 offsets (n + 1 entries, an exclusive scan) on stream st
-int scan_len16(emqx_gm_ctx* ctx, hipStream_t st, const uint16_t* len, uint64_t n, uint64_t* out);
 // gm_host.cpp: emqx_gm_match on host buffers, chunked and pipelined (H2D / match / D2H overlap)
 int run_match_host(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to, uint64_t n,
                    uint32_t flags, emqx_gm_csr* out);
@@ -605,8 +629,6 @@ struct SmallSide {
 int run_host_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to, uint64_t n,
                    uint32_t flags, emqx_gm_csr* out, emqx_gm_match_stats* st_out, SmallFan* fan = nullptr,
                    SmallSide* side = nullptr);
-int queue_fanout_spec(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint64_t* d_ro, const uint32_t* d_ids,
-                      uint64_t n, uint64_t cap_m, uint64_t cap_f, uint64_t* seg_dst, uint64_t* row_off, uint32_t* ids);
 // A host-row fan-out of a publish window, the same way (entered WITHOUT
 // ctx->mu): the rows staged outside the lock, the deliveries written into a
 // speculative capacity, one device round trip.  idx: the snapshot on this
@@ -616,8 +638,6 @@ int queue_fanout_spec(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint64_t
 // caller takes the ordinary path.
 int run_fanout_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_index* host, const emqx_gm_csr* m,
                      emqx_gm_csr* out, emqx_gm_match_stats* st_out);
-int queue_fanout_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint64_t* d_off, const uint32_t* d_ids,
-                       uint64_t n, uint64_t nnz, uint64_t total, uint64_t* seg_dst, uint64_t* row_off, uint32_t* ids);
 // A group of publish windows as ONE device batch (emqx_gm_match_windows; entered
 // WITHOUT ctx->mu, like run_host_small): the windows' text and u16 lengths
 // concatenated in one page-locked staging buffer with the window table behind

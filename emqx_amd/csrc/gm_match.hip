@@ -1,4 +1,8 @@
-// gm_match.hip — CDNA4 (gfx950) kernels for batch topic matching and fan-out.
+// gm_match.hip — CDNA4 (gfx950) kernels for batch topic matching, and the
+// match call that launches them (MatchCall: run_match / match_submit /
+// match_wait, with the knob readers and launch_* that pick the instantiations).
+// What consumes the finished rows is in gm_csr.hip, the device side of
+// in-place updates in gm_update.hip, the scan in gm_scan.h.
 //
 // Hot path (replaces emqx_trie:match/1 + emqx_router:match_routes/1,
 // apps/emqx/src/emqx_trie.erl:147-333, apps/emqx/src/emqx_router.erl:128-145):
@@ -28,11 +32,8 @@
 //                  could not hold, frontier in HBM (bounded by the node
 //                  count), matches as a bitmap over filter ids, emitted in
 //                  ascending id order.  No truncation, no CPU fallback.
-//
-// Fan-out (replaces emqx_broker:dispatch/2 + do_dispatch, emqx_broker.erl:
-// 296-322, 506-530): k_fanout_seglen -> scan -> k_fanout_copy, a load-balanced
-// CSR gather in which every workgroup owns a fixed range of OUTPUT elements,
-// so a 1M-subscriber row is split across many workgroups.
+//   k_d0_refresh   the walk's level-0 record (IndexView::d0_root), rewritten
+//                  at build and after each in-place update (refresh_d0).
 //
 // Everything here is integer/byte work bound by HBM/L2 latency and bandwidth;
 // there is no MFMA.
@@ -46,8 +47,8 @@
 #include <type_traits>
 #include <vector>
 
-#include "gm_gather.h"
 #include "gm_internal.h"
+#include "gm_scan.h"
 
 namespace gm {
 
@@ -1939,218 +1940,15 @@ __global__ __launch_bounds__(256, 8) void k_match_fused(const uint8_t* __restric
                                                     tsum, tlen, cnt8, &PH, d1);
 }
 
-// ---------------------------------------------------------------------------
-// scan (u64, exclusive, n+1 outputs: out[n] = total)
-// ---------------------------------------------------------------------------
-constexpr int SCAN_T = 256, SCAN_V = 4, SCAN_B = SCAN_T * SCAN_V;
-// one-launch form for short inputs (up to 4,096 values: a match call of up to
-// 262,144 topics): one workgroup of SCAN1_T threads, SCAN1_V per thread.  (16
-// per thread, 16,384 values, took 25.6 us against 14 us for the three-launch
-// form at C1's 15,625 tiles: one CU's address unit serializes the lanes'
-// separate lines.)
-constexpr int SCAN1_T = 1024, SCAN1_V = 4, SCAN1_B = SCAN1_T * SCAN1_V;
-
-// A second array summed alongside the scan (the main pass's per-tile probe
-// counts -> the probe counter), one atomic add per workgroup: saves the
-// separate reduction launch of a match call.
-struct SideSum {
-  const unsigned long long* a = nullptr;
-  uint64_t n = 0;
-  unsigned long long* acc = nullptr;
-};
-
-// Scan of one workgroup's T*V inputs (exclusive, from `pre`); returns the
-// workgroup's total to every thread.  s_w: T/64 + 1 words of LDS.
-template <int T, int V, class LOAD>
-__device__ __forceinline__ uint64_t block_scan(LOAD load, uint64_t base, uint64_t n_in, uint64_t n_out, uint64_t pre,
-                                               uint64_t* __restrict__ out, uint64_t* s_w, const SideSum& side) {
-  uint64_t v[V];
-  uint64_t run = 0, ssum = 0;
-#pragma unroll
-  for (int k = 0; k < V; ++k) {
-    const uint64_t i = base + k;
-    const uint64_t x = i < n_in ? load(i) : 0;
-    v[k] = run;
-    run += x;
-    if (side.a && i < side.n) ssum += side.a[i];
-  }
-  // wave inclusive scan of per-thread totals
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint64_t x = run;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  if (side.a) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) ssum += __shfl_down(ssum, d, 64);
-  }
-  if (lane == 63) s_w[wv] = x;
-  if (side.a && lane == 0) s_w[T / 64 + wv] = ssum;
-  __syncthreads();
-  uint64_t wpre = 0, tot = 0;
-  for (int k = 0; k < T / 64; ++k) {
-    wpre += k < wv ? s_w[k] : 0;
-    tot += s_w[k];
-  }
-  const uint64_t tpre = pre + wpre + x - run;
-#pragma unroll
-  for (int k = 0; k < V; ++k) {
-    const uint64_t i = base + k;
-    if (i < n_out) out[i] = tpre + v[k];
-  }
-  if (side.a && threadIdx.x == 0) {
-    uint64_t st = 0;
-    for (int k = 0; k < T / 64; ++k) st += s_w[T / 64 + k];
-    if (st) atomicAdd(side.acc, (unsigned long long)st);
-  }
-  return tot;
-}
-
+// ---- the match call's pass counters; its scan is gm_scan.h's scan_excl -----
 __global__ void k_zero16(uint32_t* __restrict__ p) {  // 16 words (64 B)
   if (threadIdx.x < 16) p[threadIdx.x] = 0u;
 }
 
-template <class LOAD>
-__global__ __launch_bounds__(SCAN_T) void k_scan_local(LOAD load, uint64_t n_in, uint64_t n_out,
-                                                        uint64_t* __restrict__ out,
-                                                        uint64_t* __restrict__ block_sums, SideSum side) {
-  __shared__ uint64_t s_w[2 * (SCAN_T / 64)];
-  const uint64_t base = uint64_t(blockIdx.x) * SCAN_B + threadIdx.x * SCAN_V;
-  const uint64_t tot = block_scan<SCAN_T, SCAN_V>(load, base, n_in, n_out, 0, out, s_w, side);
-  if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
-}
-
-template <class LOAD>
-__global__ __launch_bounds__(SCAN1_T) void k_scan_one(LOAD load, uint64_t n_in, uint64_t n_out,
-                                                       uint64_t* __restrict__ out, SideSum side,
-                                                       uint64_t* __restrict__ mirror) {
-  __shared__ uint64_t s_w[2 * (SCAN1_T / 64)];
-  const uint64_t tot = block_scan<SCAN1_T, SCAN1_V>(load, uint64_t(threadIdx.x) * SCAN1_V, n_in, n_out, 0, out, s_w,
-                                                    side);
-  if (mirror && threadIdx.x == 0) *mirror = tot;  // the grand total, also at the caller's out[n]
-}
-
-// A small call's scan of up to 8 x SCAN1_B values in ONE launch: the workgroup
-// walks the chunks with a running carry (a publish window's fan-out: ~5-15k
-// matches, where the three-launch form idled the queue ~20 us between launches)
-template <class LOAD>
-__global__ __launch_bounds__(SCAN1_T) void k_scan_loop(LOAD load, uint64_t n_in, uint64_t n_out,
-                                                        uint64_t* __restrict__ out) {
-  __shared__ uint64_t s_w[2 * (SCAN1_T / 64)];
-  uint64_t pre = 0;
-  for (uint64_t b0 = 0; b0 < n_out; b0 += SCAN1_B) {
-    pre += block_scan<SCAN1_T, SCAN1_V>(load, b0 + uint64_t(threadIdx.x) * SCAN1_V, n_in, n_out, pre, out, s_w,
-                                        SideSum{});
-    __syncthreads();  // (s_w is rewritten by the next chunk)
-  }
-}
-constexpr uint64_t SCAN_LOOP_MAX = 8ull * SCAN1_B;
-
-__global__ __launch_bounds__(SCAN_T) void k_scan_add(uint64_t* __restrict__ out, uint64_t n_out,
-                                                      const uint64_t* __restrict__ block_off) {
-  const uint64_t base = uint64_t(blockIdx.x) * SCAN_B;
-  const uint64_t add = block_off[blockIdx.x];
-  for (int k = threadIdx.x; k < SCAN_B; k += SCAN_T) {
-    const uint64_t i = base + k;
-    if (i < n_out) out[i] += add;
-  }
-}
-
-struct LoadU64 {
-  const uint64_t* p;
-  __device__ uint64_t operator()(uint64_t i) const { return p[i]; }
-};
 struct LoadCnt {  // masked match counts
   const uint32_t* p;
   __device__ uint64_t operator()(uint64_t i) const { return p[i] & CNT_MASK; }
 };
-struct LoadSegLen {  // subscriber count of the filter of match entry i
-  const uint32_t* ids;
-  const uint64_t* sub_off;
-  __device__ uint64_t operator()(uint64_t i) const {
-    const uint32_t f = ids[i];
-    return sub_off[f + 1] - sub_off[f];
-  }
-};
-
-// LoadSegLen over a small call's SPECULATIVE rows (emqx_gm_match_fanout): the
-// fan-out is queued before the host knows the match count, so entries past the
-// device's own count (*nnz, the rows' row_off[n]) and ids out of range (an
-// overflowed speculative buffer holds stale words) count 0 -- such a fan-out
-// is discarded, but it reads nothing out of bounds
-struct LoadSegLenSpec {
-  const uint32_t* ids;
-  const uint64_t* sub_off;
-  const uint64_t* nnz;
-  uint32_t nf;
-  __device__ uint64_t operator()(uint64_t i) const {
-    if (i >= *nnz) return 0;
-    const uint32_t f = ids[i];
-    return f < nf ? sub_off[f + 1] - sub_off[f] : 0;
-  }
-};
-
-// Exclusive scan of n_in loaded values into out[0..n_in] (out[n_in] = total).
-// split (optional): for a two-level scan, leave out[0..n_in) block-local and
-// hand back the blocks' offsets in *split (out[i] + (*split)[i / SCAN_B] is the
-// scan; out[n_in] is the grand total) -- the consumer adds them, one launch
-// (k_scan_add) fewer.  split->p stays null when the scan was not split.
-// st: the stream (default: the context's).  On another stream the scan's
-// workspace goes back to the pool behind an event on that stream (the pool's
-// immediate reuse assumes the context stream's order).
-// split_sums (optional, with split): a scan of at most 64 blocks may hand
-// back the blocks' SUMS instead (*split_sums = their count): no second launch;
-// the consumer (k_assemble_c) sums the prefixes and writes out[n_in] itself.
-template <class LOAD>
-int scan_excl(emqx_gm_ctx* ctx, LOAD load, uint64_t n_in, uint64_t* out, SideSum side = SideSum{},
-              PoolBuf* split = nullptr, hipStream_t st = nullptr, uint32_t* split_sums = nullptr) {
-  if (split_sums) *split_sums = 0;
-  if (!st) st = ctx->stream;
-  const uint64_t n_out = n_in + 1;
-  if (n_out <= uint64_t(SCAN1_B)) {  // one launch
-    hipLaunchKernelGGL(k_scan_one<LOAD>, dim3(1), dim3(SCAN1_T), 0, st, load, n_in, n_out, out, side,
-                       static_cast<uint64_t*>(nullptr));
-    GM_HIP(ctx, hipGetLastError());
-    return 0;
-  }
-  const uint64_t nb = (n_out + SCAN_B - 1) / SCAN_B;
-  PoolBuf sums(ctx->pool, nb * 8 + 8), offs(ctx->pool, (nb + 1) * 8 + 8);
-  if (!sums.p || !offs.p) return set_err(ctx, EMQX_GM_ENOMEM, "scan: workspace");
-  struct Later {  // (another stream: release the workspace behind that stream's work)
-    emqx_gm_ctx* c;
-    hipStream_t s;
-    PoolBuf* b[2];
-    ~Later() {
-      if (s == c->stream) return;
-      for (PoolBuf* x : b)
-        if (x->p) c->pool->release_after(x->release_ownership(), s);
-    }
-  } later{ctx, st, {&sums, &offs}};
-  hipLaunchKernelGGL(k_scan_local<LOAD>, dim3(nb), dim3(SCAN_T), 0, st, load, n_in, n_out, out,
-                     sums.as<uint64_t>(), side);
-  if (split && split_sums && nb <= 64) {
-    GM_HIP(ctx, hipGetLastError());
-    *split = std::move(sums);
-    *split_sums = uint32_t(nb);
-    return 0;
-  }
-  if (split && nb + 1 <= uint64_t(SCAN1_B)) {  // the blocks' offsets, and the total into out[n_in]
-    hipLaunchKernelGGL(k_scan_one<LoadU64>, dim3(1), dim3(SCAN1_T), 0, st, LoadU64{sums.as<uint64_t>()}, nb,
-                       nb + 1, offs.as<uint64_t>(), SideSum{}, out + n_in);
-    GM_HIP(ctx, hipGetLastError());
-    *split = std::move(offs);
-    return 0;
-  }
-  if (nb > 1) {
-    int rc = scan_excl(ctx, LoadU64{sums.as<uint64_t>()}, nb, offs.as<uint64_t>(), SideSum{}, nullptr, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(SCAN_T), 0, st, out, n_out, offs.as<uint64_t>());
-  }
-  GM_HIP(ctx, hipGetLastError());
-  return 0;
-}
 
 // ---------------------------------------------------------------------------
 // assembly
@@ -2583,872 +2381,8 @@ __global__ __launch_bounds__(256) void k_copy_slow(const uint32_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------
-// fan-out
-// ---------------------------------------------------------------------------
-// (nseg: the segments seg_dst holds -- a speculative call's row offsets may point past them)
-__global__ __launch_bounds__(256) void k_fanout_rowoff(const uint64_t* __restrict__ m_off, uint64_t n,
-                                                       const uint64_t* __restrict__ seg_dst,
-                                                       uint64_t* __restrict__ out_off, uint64_t nseg) {
-  const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
-  if (i <= n) out_off[i] = seg_dst[min(m_off[i], nseg)];
-}
-
-// Output elements per workgroup: from 1,024 (a publish window's ~100k
-// deliveries in ~100 workgroups, not 30: 63 -> ~20 us) up to 65,536 for large
-// fan-outs (C4: 0.94 -> 0.81 ms against 4,096, fewer per-block segment
-// searches), a multiple of 1,024 (4 per thread step).
-inline uint64_t fan_per_block(uint64_t total) {
-  uint64_t per = total / 2048;  // ~8 workgroups per CU
-  per = per < 1024 ? 1024 : per > 65536 ? 65536 : per;
-  return (per + 1023) & ~uint64_t(1023);
-}
-
-// Segment of output element p: the last segment whose start <= p, searched in
-// [a, b] (the block's first and last segments).
-__device__ __forceinline__ uint64_t fan_seg(const uint64_t* __restrict__ seg_dst, uint64_t a, uint64_t b, uint64_t p) {
-  if (a == b) return a;
-  ++b;
-  while (b - a > 1) {
-    const uint64_t m = (a + b) >> 1;
-    if (seg_dst[m] <= p) a = m;
-    else b = m;
-  }
-  return a;
-}
-
-// Every workgroup owns per_block consecutive output elements; a thread
-// moves 4 consecutive elements at a time, as one 16-B non-temporal store (the
-// output is streamed out once) when they lie in one segment -- the usual case,
-// a hot row being one long segment -- and element by element across a
-// segment boundary.
-__global__ __launch_bounds__(256) void k_fanout_copy(const uint64_t* __restrict__ seg_dst, uint64_t nseg,
-                                                     const uint32_t* __restrict__ m_ids,
-                                                     const uint64_t* __restrict__ sub_off,
-                                                     const uint32_t* __restrict__ sub_ids, uint64_t glo,
-                                                     uint64_t total, uint64_t per_block, uint32_t* __restrict__ out0,
-                                                     bool clamp) {
-  // this launch produces the global delivery range [glo, total); out0[0] is delivery glo
-  // (clamp: never past the device's own total -- a small host fan-out sizes
-  // the launch by a speculative capacity, gm_host.cpp run_fanout_small)
-  if (clamp) total = min(total, seg_dst[nseg]);
-  const uint64_t lo = glo + uint64_t(blockIdx.x) * per_block;
-  if (lo >= total) return;
-  const uint64_t hi = min(total, lo + per_block);
-  uint32_t* const out = out0 - glo;  // indexed by global delivery number
-  __shared__ uint64_t s_seg[2];
-  if (threadIdx.x < 2) {
-    // last segment whose start <= x (segments may be empty)
-    const uint64_t x = threadIdx.x == 0 ? lo : hi - 1;
-    uint64_t a = 0, b = nseg;  // seg_dst[a] <= x < seg_dst[b]
-    while (b - a > 1) {
-      const uint64_t m = (a + b) >> 1;
-      if (seg_dst[m] <= x) a = m;
-      else b = m;
-    }
-    s_seg[threadIdx.x] = a;
-  }
-  __syncthreads();
-  const uint64_t s0 = s_seg[0], s1 = s_seg[1];
-  if (s0 == s1) {
-    // the whole range lies in one segment (a hot row): the source offset is
-    // loop invariant, so each step is an independent load + store with no
-    // dependent segment lookups in between
-    const uint64_t off = sub_off[m_ids[s0]] - seg_dst[s0];  // element q comes from sub_ids[off + q] (mod 2^64)
-    uint64_t q = lo + uint64_t(threadIdx.x) * 4;
-    for (; q + 4 <= hi; q += 256 * 4) {
-      const uint32_t* src = sub_ids + (off + q);
-      const uint4 v = make_uint4(src[0], src[1], src[2], src[3]);
-      __builtin_nontemporal_store(v.x, out + q);
-      __builtin_nontemporal_store(v.y, out + q + 1);
-      __builtin_nontemporal_store(v.z, out + q + 2);
-      __builtin_nontemporal_store(v.w, out + q + 3);
-    }
-    for (uint64_t p = q; p < hi; ++p) out[p] = sub_ids[off + p];  // q + 4 > hi here: at most 3 left
-    return;
-  }
-  for (uint64_t q = lo + uint64_t(threadIdx.x) * 4; q < hi; q += 256 * 4) {
-    const uint64_t s = fan_seg(seg_dst, s0, s1, q);
-    const uint64_t sd = seg_dst[s];
-    if (q + 4 <= hi && q + 4 <= seg_dst[s + 1]) {
-      const uint32_t* src = sub_ids + sub_off[m_ids[s]] + (q - sd);
-      const uint4 v = make_uint4(src[0], src[1], src[2], src[3]);
-      __builtin_nontemporal_store(v.x, out + q);
-      __builtin_nontemporal_store(v.y, out + q + 1);
-      __builtin_nontemporal_store(v.z, out + q + 2);
-      __builtin_nontemporal_store(v.w, out + q + 3);
-    } else {
-      for (uint64_t p = q; p < q + 4 && p < hi; ++p) {
-        const uint64_t sp = fan_seg(seg_dst, s0, s1, p);
-        out[p] = sub_ids[sub_off[m_ids[sp]] + (p - seg_dst[sp])];
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// stats helper: sum of matched filter lengths (for algorithmic bytes)
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* a, uint32_t n, uint32_t x) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t m = (lo + hi) >> 1;
-    if (a[m] < x) lo = m + 1;
-    else hi = m;
-  }
-  return lo;
-}
-
-__global__ __launch_bounds__(256) void k_sum_flen(const uint32_t* __restrict__ ids, uint64_t nnz,
-                                                  const uint16_t* __restrict__ flen,
-                                                  const uint32_t* __restrict__ gmap, uint32_t nf,
-                                                  unsigned long long* __restrict__ acc) {
-  uint64_t s = 0;
-  for (uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x; i < nnz; i += uint64_t(gridDim.x) * 256u)
-    s += flen[gmap ? lower_bound_u32(gmap, nf, ids[i]) : ids[i]];
-  for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
-  if ((threadIdx.x & 63) == 0) atomicAdd(acc, (unsigned long long)s);
-}
-
-// ---------------------------------------------------------------------------
-// row merge (sharded index)
-// ---------------------------------------------------------------------------
-// Pieces p = 0..P-1 each hold, for the same n rows, a sorted list of filter
-// ids; the lists of one row are disjoint (filters are partitioned over the
-// shards).  lens is [P][stride] (rows >= n have length 0), ids the pieces'
-// rows concatenated piece-major, row-minor (the all-to-all's output), so an
-// exclusive scan of lens gives every (piece, row) list's offset in ids.  Each
-// element's rank in its merged row = its index in its own list + its
-// lower_bound in every other list of the row.
-struct LoadU32 {
-  const uint32_t* p;
-  __device__ uint64_t operator()(uint64_t i) const { return p[i]; }
-};
-struct LoadRowSum {  // merged row length
-  const uint32_t* lens;
-  uint64_t stride;
-  uint32_t pieces;
-  __device__ uint64_t operator()(uint64_t t) const {
-    uint64_t s = 0;
-    for (uint32_t p = 0; p < pieces; ++p) s += lens[p * stride + t];
-    return s;
-  }
-};
-
-__global__ __launch_bounds__(256) void k_merge_rows(const uint32_t* __restrict__ lens, const uint64_t* __restrict__ pos,
-                                                    const uint32_t* __restrict__ ids, uint64_t n, uint64_t stride,
-                                                    uint32_t pieces, const uint64_t* __restrict__ row_off,
-                                                    uint32_t* __restrict__ out) {
-  const uint64_t t = uint64_t(blockIdx.x) * 256u + threadIdx.x;
-  if (t >= n) return;
-  const uint64_t o = row_off[t];
-  for (uint32_t p = 0; p < pieces; ++p) {
-    const uint64_t src = pos[p * stride + t];
-    const uint32_t len = lens[p * stride + t];
-    for (uint32_t j = 0; j < len; ++j) {
-      const uint32_t x = ids[src + j];
-      uint64_t r = j;
-      for (uint32_t q = 0; q < pieces; ++q)
-        if (q != p) r += lower_bound_u32(ids + pos[q * stride + t], lens[q * stride + t], x);
-      out[o + r] = x;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void k_row_lengths(const uint64_t* __restrict__ row_off, uint64_t n,
-                                                     uint32_t* __restrict__ out) {
-  const uint64_t t = uint64_t(blockIdx.x) * 256u + threadIdx.x;
-  if (t < n) out[t] = uint32_t(row_off[t + 1] - row_off[t]);
-}
-
-// ---------------------------------------------------------------------------
-// overlay snapshot merge (incremental updates, gm_overlay.cpp)
-// ---------------------------------------------------------------------------
-struct OvView {
-  const uint32_t* tbm;   // tombstone bitmap over base ids
-  const uint32_t* tpre;  // tombstones in the words before each bitmap word
-  const uint32_t* ins;   // insertion point of each delta filter, ascending
-  uint32_t n_ins;
-};
-__device__ __forceinline__ bool ov_dead(const OvView& o, uint32_t b) { return (o.tbm[b >> 5] >> (b & 31)) & 1u; }
-// final id of a surviving base id: + delta filters sorting before it - tombstones below it
-__device__ __forceinline__ uint32_t ov_remap(const OvView& o, uint32_t b) {
-  uint32_t lo = 0, hi = o.n_ins;
-  while (lo < hi) {
-    const uint32_t m = (lo + hi) >> 1;
-    if (o.ins[m] <= b) lo = m + 1;
-    else hi = m;
-  }
-  const uint32_t w = b >> 5;
-  return b + lo - (o.tpre[w] + __popc(o.tbm[w] & ((1u << (b & 31)) - 1u)));
-}
-struct LoadOvLen {  // merged row length: surviving base ids + delta ids
-  const uint64_t* bo;
-  const uint32_t* bi;
-  const uint64_t* dof;
-  OvView o;
-  __device__ uint64_t operator()(uint64_t t) const {
-    uint64_t c = dof ? dof[t + 1] - dof[t] : 0;
-    for (uint64_t k = bo[t]; k < bo[t + 1]; ++k) c += ov_dead(o, bi[k]) ? 0 : 1;
-    return c;
-  }
-};
-__global__ __launch_bounds__(256) void k_ov_merge(const uint64_t* __restrict__ bo, const uint32_t* __restrict__ bi,
-                                                  const uint64_t* __restrict__ dof, const uint32_t* __restrict__ di,
-                                                  OvView o, uint64_t n, const uint64_t* __restrict__ row_off,
-                                                  uint32_t* __restrict__ out) {
-  const uint64_t t = uint64_t(blockIdx.x) * 256u + threadIdx.x;
-  if (t >= n) return;
-  uint64_t i = bo[t], w = row_off[t];
-  const uint64_t ie = bo[t + 1];
-  uint64_t j = dof ? dof[t] : 0;
-  const uint64_t je = dof ? dof[t + 1] : 0;
-  auto next_base = [&]() -> uint32_t {
-    while (i < ie && ov_dead(o, bi[i])) ++i;
-    return i < ie ? ov_remap(o, bi[i]) : 0xFFFFFFFFu;
-  };
-  uint32_t b = next_base(), d = j < je ? di[j] : 0xFFFFFFFFu;
-  while (b != 0xFFFFFFFFu || d != 0xFFFFFFFFu) {
-    if (b < d) {
-      out[w++] = b;
-      ++i;
-      b = next_base();
-    } else {
-      out[w++] = d;
-      ++j;
-      d = j < je ? di[j] : 0xFFFFFFFFu;
-    }
-  }
-}
-
-// Offsets of the host-buffer path: topics cross PCIe with u32 chunk-relative
-// offsets (4 B per topic instead of 8) and rows come back the same way.
-__global__ __launch_bounds__(256) void k_off32_to_64(const uint32_t* __restrict__ in, uint64_t n1,
-                                                     uint64_t* __restrict__ out) {
-  for (uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x; i < n1; i += uint64_t(gridDim.x) * 256u) out[i] = in[i];
-}
-__global__ __launch_bounds__(256) void k_off64_to_32(const uint64_t* __restrict__ in, uint64_t n1,
-                                                     uint32_t* __restrict__ out) {
-  for (uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x; i < n1; i += uint64_t(gridDim.x) * 256u)
-    out[i] = uint32_t(in[i]);
-}
-int launch_off32_to_64(hipStream_t st, const uint32_t* in, uint64_t n1, uint64_t* out) {
-  const uint64_t g = std::min<uint64_t>(2048, (n1 + 255) / 256);
-  hipLaunchKernelGGL(k_off32_to_64, dim3(g ? g : 1), dim3(256), 0, st, in, n1, out);
-  return hipGetLastError() == hipSuccess ? 0 : EMQX_GM_EDEVICE;
-}
-int launch_off64_to_32(hipStream_t st, const uint64_t* in, uint64_t n1, uint32_t* out) {
-  const uint64_t g = std::min<uint64_t>(2048, (n1 + 255) / 256);
-  hipLaunchKernelGGL(k_off64_to_32, dim3(g ? g : 1), dim3(256), 0, st, in, n1, out);
-  return hipGetLastError() == hipSuccess ? 0 : EMQX_GM_EDEVICE;
-}
-// Small host-buffer calls (gm_host.cpp run_host_small): inputs in and rows out
-// through page-locked host memory the device addresses directly -- two copies
-// in one launch on the call's own queue, so no copy engine has to hand over to
-// the compute queue between the call's kernels (~10 us a hand-over).  n1_max
-// (optional): the second copy stops at the count the device wrote there (a
-// result's row_off[n]: the rows' true length inside a speculative capacity)
-__global__ __launch_bounds__(256) void k_copy_u32x2(const uint32_t* __restrict__ s0, uint32_t* __restrict__ d0,
-                                                    uint64_t n0, const uint32_t* __restrict__ s1,
-                                                    uint32_t* __restrict__ d1, uint64_t n1,
-                                                    const uint64_t* __restrict__ n1_max) {
-  if (n1_max) n1 = min(n1, *n1_max);
-  const uint64_t t = uint64_t(blockIdx.x) * 256u + threadIdx.x, stride = uint64_t(gridDim.x) * 256u;
-  const uint64_t q0 = n0 / 4, q1 = n1 / 4;  // (16-B units; every buffer here is 16-B aligned)
-  for (uint64_t i = t; i < q0; i += stride)
-    reinterpret_cast<uint4*>(d0)[i] = reinterpret_cast<const uint4*>(s0)[i];
-  for (uint64_t i = t; i < q1; i += stride)
-    reinterpret_cast<uint4*>(d1)[i] = reinterpret_cast<const uint4*>(s1)[i];
-  if (t < (n0 & 3)) d0[q0 * 4 + t] = s0[q0 * 4 + t];
-  if (t < (n1 & 3)) d1[q1 * 4 + t] = s1[q1 * 4 + t];
-  __threadfence_system();  // (host-bound stores visible before the call's end event)
-}
-int launch_copy_u32x2(hipStream_t st, const uint32_t* s0, uint32_t* d0, uint64_t n0, const uint32_t* s1, uint32_t* d1,
-                      uint64_t n1, const uint64_t* n1_max) {
-  const uint64_t q = (std::max(n0, n1) + 3) / 4;
-  const uint64_t g = std::min<uint64_t>(1024, (q + 255) / 256);
-  hipLaunchKernelGGL(k_copy_u32x2, dim3(g ? g : 1), dim3(256), 0, st, s0, d0, n0, s1, d1, n1, n1_max);
-  return hipGetLastError() == hipSuccess ? 0 : EMQX_GM_EDEVICE;
-}
-// p[0..n1) += add, in place (a chunk's row offsets rebased to the whole call's rows)
-__global__ __launch_bounds__(256) void k_add_u64(uint64_t* __restrict__ p, uint64_t n1, uint64_t add) {
-  for (uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x; i < n1; i += uint64_t(gridDim.x) * 256u) p[i] += add;
-}
-int launch_add_u64(hipStream_t st, uint64_t* p, uint64_t n1, uint64_t add) {
-  if (!n1) return 0;
-  const uint64_t g = std::min<uint64_t>(2048, (n1 + 255) / 256);
-  hipLaunchKernelGGL(k_add_u64, dim3(g), dim3(256), 0, st, p, n1, add);
-  return hipGetLastError() == hipSuccess ? 0 : EMQX_GM_EDEVICE;
-}
-
-// ---- in-place update (gm_overlay.cpp, patch_update) -----------------------
-// The host-patched byte ranges, cut into pieces of <= PATCH_PIECE bytes, one
-// workgroup per piece: desc[3b..3b+2] = (offset in the blob, offset in the
-// payload, bytes).
-constexpr uint32_t PATCH_PIECE = 4096;
-__global__ __launch_bounds__(256) void k_patch_scatter(uint8_t* __restrict__ dst, const uint64_t* __restrict__ desc,
-                                                       const uint8_t* __restrict__ pay) {
-  const uint64_t d = desc[3 * blockIdx.x], p = desc[3 * blockIdx.x + 1], n = desc[3 * blockIdx.x + 2];
-  for (uint64_t i = threadIdx.x; i < n; i += 256) dst[d + i] = pay[p + i];
-}
-// The id table of an in-place update (IdShift::map, gm_internal.h), built on
-// the device from the O(delta) lists: dels (prev ids deleted, ascending) and
-// addpos (per new filter, byte order: prev filters sorting before it).
-__device__ __forceinline__ uint32_t count_below(const uint32_t* a, uint32_t n, uint32_t x) {  // a[i] < x
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t m = (lo + hi) >> 1;
-    if (a[m] < x) lo = m + 1;
-    else hi = m;
-  }
-  return lo;
-}
-__global__ __launch_bounds__(256) void k_shift_table(uint32_t* __restrict__ rmap, uint64_t nb,
-                                                     const uint32_t* __restrict__ dels, uint32_t nd,
-                                                     const uint32_t* __restrict__ addpos, uint32_t na) {
-  const uint64_t id = uint64_t(blockIdx.x) * 256u + threadIdx.x;
-  if (id >= nb + na) return;
-  if (id >= nb) {
-    const uint32_t k = uint32_t(id - nb), p = addpos[k];
-    rmap[id] = p - count_below(dels, nd, p) + k;
-    return;
-  }
-  const uint32_t x = uint32_t(id), below = count_below(dels, nd, x);
-  if (below < nd && dels[below] == x) {
-    rmap[id] = NONE;
-    return;
-  }
-  rmap[id] = x - below + count_below(addpos, na, x + 1);  // inserts at or before it
-}
-// A shard's new local-to-global id map after a sharded update (gm_shard.cpp,
-// GmapJob): rows leave the device through view.gmap[local id], and one insert
-// anywhere shifts global ids on every shard.  For every old or temporary local
-// id i < nb + na: j = rmap[i] (the shard's local shift, k_shift_table's table;
-// nullptr: the identity; NONE: deleted), new_gmap[j] = G(old_gmap[i]) for a
-// surviving filter, add_gid[i - nb] for a new one, with G(g) = g - (gdels < g)
-// + (gadds <= g) the GLOBAL shift.  old_gmap ascends, so the 256 elements of a
-// tile bracket a narrow window of gdels / gadds: four lanes find it with full
-// searches on the tile's first and last element, the windows are staged in LDS
-// when they fit, and each lane searches only inside them.  A streaming pass:
-// 4 B read and 4 B written per filter (writes monotone in i).
-constexpr uint32_t GMAP_WIN = 1024;
-__global__ __launch_bounds__(256) void k_gmap_shift(const uint32_t* __restrict__ old_gmap, uint32_t nb, uint32_t na,
-                                                    const uint32_t* __restrict__ rmap,
-                                                    const uint32_t* __restrict__ add_gid,
-                                                    const uint32_t* __restrict__ gdels, uint32_t gnd,
-                                                    const uint32_t* __restrict__ gadds, uint32_t gna,
-                                                    uint32_t* __restrict__ new_gmap, uint32_t n_new) {
-  __shared__ uint32_t s_d[GMAP_WIN], s_a[GMAP_WIN];
-  __shared__ uint32_t s_w[4];  // dels window [0], [1]; adds window [2], [3]
-  const uint64_t n_map = uint64_t(nb) + na;
-  for (uint64_t base = uint64_t(blockIdx.x) * 256u; base < n_map; base += uint64_t(gridDim.x) * 256u) {
-    uint32_t d_lo = 0, d_hi = 0, a_lo = 0, a_hi = 0;
-    bool ld = false, la = false;
-    if (base < nb) {  // (block-uniform) the tile's old ids: [base, hi)
-      const uint32_t hi = uint32_t(min(base + 256u, uint64_t(nb)));
-      if (threadIdx.x < 4) {
-        const uint32_t g = old_gmap[(threadIdx.x & 1) ? hi - 1 : uint32_t(base)];
-        s_w[threadIdx.x] = threadIdx.x < 2 ? count_below(gdels, gnd, g) : count_below(gadds, gna, g + 1);
-      }
-      __syncthreads();
-      d_lo = s_w[0], d_hi = max(s_w[0], s_w[1]), a_lo = s_w[2], a_hi = max(s_w[2], s_w[3]);
-      ld = d_hi - d_lo <= GMAP_WIN;
-      la = a_hi - a_lo <= GMAP_WIN;
-      if (ld)
-        for (uint32_t k = threadIdx.x; k < d_hi - d_lo; k += 256) s_d[k] = gdels[d_lo + k];
-      if (la)
-        for (uint32_t k = threadIdx.x; k < a_hi - a_lo; k += 256) s_a[k] = gadds[a_lo + k];
-      __syncthreads();
-    }
-    const uint64_t i = base + threadIdx.x;
-    if (i < n_map) {
-      const uint32_t j = rmap ? rmap[i] : uint32_t(i);
-      if (j != NONE && j < n_new) {
-        if (i >= nb) {
-          new_gmap[j] = add_gid[i - nb];
-        } else {
-          const uint32_t g = old_gmap[i];
-          const uint32_t below = d_lo + (ld ? count_below(s_d, d_hi - d_lo, g) : count_below(gdels + d_lo, d_hi - d_lo, g));
-          const uint32_t ins =
-              a_lo + (la ? count_below(s_a, a_hi - a_lo, g + 1) : count_below(gadds + a_lo, a_hi - a_lo, g + 1));
-          new_gmap[j] = g - below + ins;
-        }
-      }
-    }
-    __syncthreads();  // (the next tile restages the windows)
-  }
-}
-// Flag bits set on words whose other bits are filter ids (HOT_PLUS on hf /
-// p_hf): the host mirror's ids are stale (not renumbered), so these go as ORs.
-__global__ __launch_bounds__(256) void k_patch_or(uint32_t* __restrict__ dst, const uint64_t* __restrict__ ops,
-                                                  uint64_t n) {
-  const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t off = ops[2 * i];
-  if (off & PATCH_AND) atomicAnd(dst + ((off & ~PATCH_AND) >> 2), ~uint32_t(ops[2 * i + 1]));
-  else atomicOr(dst + (off >> 2), uint32_t(ops[2 * i + 1]));
-}
-// Every filter-id field renumbered (renum_field, the device twin of
-// gm_overlay.cpp's renumber_host): hot slots [0, n_hot), nodes [0, n_nodes).
-__global__ __launch_bounds__(256) void k_renumber(HotSlot* __restrict__ hot, uint64_t n_hot, Node* __restrict__ nodes,
-                                                  uint64_t n_nodes, const uint32_t* __restrict__ rmap) {
-  const uint64_t stride = uint64_t(gridDim.x) * 256u;
-  for (uint64_t s = uint64_t(blockIdx.x) * 256u + threadIdx.x; s < n_hot; s += stride) {
-    HotSlot h = hot[s];
-    if (h.key == EDGE_EMPTY) continue;
-    h.hf = renum_field(h.hf, HF_NONE, HF_FLAGS, rmap);
-    h.end_filter = renum_field(h.end_filter, NONE, END_WILD, rmap);
-    h.p_hf = renum_field(h.p_hf, HF_NONE, HF_FLAGS, rmap);
-    h.p_end = renum_field(h.p_end, NONE, END_WILD, rmap);
-    hot[s] = h;
-  }
-  for (uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x; i < n_nodes; i += stride) {
-    Node nd = nodes[i];
-    nd.hash_filter = renum_field(nd.hash_filter, NONE, 0, rmap);
-    nd.end_filter = renum_field(nd.end_filter, NONE, 0, rmap);
-    nodes[i] = nd;
-  }
-}
-
-// k_renumber fused with the blob copy: dst's hot slots and nodes = src's,
-// renumbered (every slot written, empty ones as they are), so an update reads
-// and writes the id-bearing tables once instead of copying them and then
-// renumbering them in place (C5: ~26 of the 38 GB blob)
-__global__ __launch_bounds__(256) void k_renumber_copy(const HotSlot* __restrict__ shot, HotSlot* __restrict__ hot,
-                                                       uint64_t n_hot, const Node* __restrict__ snodes,
-                                                       Node* __restrict__ nodes, uint64_t n_nodes,
-                                                       const uint32_t* __restrict__ rmap) {
-  const uint64_t stride = uint64_t(gridDim.x) * 256u;
-  for (uint64_t s = uint64_t(blockIdx.x) * 256u + threadIdx.x; s < n_hot; s += stride) {
-    HotSlot h = shot[s];
-    if (h.key != EDGE_EMPTY) {
-      h.hf = renum_field(h.hf, HF_NONE, HF_FLAGS, rmap);
-      h.end_filter = renum_field(h.end_filter, NONE, END_WILD, rmap);
-      h.p_hf = renum_field(h.p_hf, HF_NONE, HF_FLAGS, rmap);
-      h.p_end = renum_field(h.p_end, NONE, END_WILD, rmap);
-    }
-    hot[s] = h;
-  }
-  for (uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x; i < n_nodes; i += stride) {
-    Node nd = snodes[i];
-    nd.hash_filter = renum_field(nd.hash_filter, NONE, 0, rmap);
-    nd.end_filter = renum_field(nd.end_filter, NONE, 0, rmap);
-    nodes[i] = nd;
-  }
-}
-
-namespace {
-// The filter-id fields of the records k_renumber rewrites: (offset, empty value, flag bits)
-struct IdField {
-  uint32_t off, none, flag;
-};
-constexpr IdField kHotIds[] = {{offsetof(HotSlot, hf), HF_NONE, HF_FLAGS},
-                               {offsetof(HotSlot, end_filter), NONE, END_WILD},
-                               {offsetof(HotSlot, p_hf), HF_NONE, HF_FLAGS},
-                               {offsetof(HotSlot, p_end), NONE, END_WILD}};
-constexpr IdField kNodeIds[] = {{offsetof(Node, hash_filter), NONE, 0u}, {offsetof(Node, end_filter), NONE, 0u}};
-// The id fields of the table [o, o + n * rec) lying inside the patched range
-// [a, b) (buf = its bytes), renumbered in place by the shift (IdShift::map:
-// O(log delta) per field).  false: a field holds an id outside the shift.
-template <size_t K>
-bool renum_payload(uint8_t* buf, uint64_t a, uint64_t b, uint64_t o, uint64_t n, uint64_t rec,
-                   const IdField (&fs)[K], const IdShift& sh, uint64_t n_map) {
-  const uint64_t lo = std::max(a, o), hi = std::min(b, o + n * rec);
-  for (uint64_t r = lo < hi ? (lo - o) / rec : 0, re = lo < hi ? (hi - o + rec - 1) / rec : 0; r < re; ++r)
-    for (const IdField& f : fs) {
-      const uint64_t at = o + r * rec + f.off;
-      if (at < a || at + 4 > b) continue;  // (the patcher writes id fields whole)
-      uint32_t x;
-      std::memcpy(&x, buf + (at - a), 4);
-      const uint32_t id = x & ~f.flag;
-      if (x != f.none && id != (f.none & ~f.flag) && id >= n_map) return false;
-      x = renum_field(x, f.none, f.flag, sh);
-      std::memcpy(buf + (at - a), &x, 4);
-    }
-  return true;
-}
-}  // namespace
-
-namespace {
-// k_gmap_shift queued on ctx's stream: the global shift's lists and the new
-// filters' ids go up in one copy (stage / dbuf: kept by the caller until it has
-// synchronized the stream); rmap: the local shift's device table (n_map
-// entries), or nullptr for a shard without local changes.
-int queue_gmap_shift(emqx_gm_ctx* ctx, const GmapJob& job, const uint32_t* rmap, uint64_t n_map,
-                     std::vector<uint32_t>& stage, PoolBuf& dbuf) {
-  const IdShift& G = *job.sh.G;
-  const std::vector<uint32_t>& ag = *job.sh.add_gid;
-  const uint64_t gnd = G.dels.size(), gna = G.addpos.size(), na = ag.size();
-  if (job.nb + na != n_map || (!rmap && na) || (job.nb && !job.old_gmap) || !job.new_gmap ||
-      job.nb + na >= 0xFFFFFFFFull || G.nb + gna >= 0xFFFFFFFFull)
-    return set_err(ctx, EMQX_GM_EINVAL, "index_update: id map job");
-  if (!n_map) return EMQX_GM_OK;
-  stage.resize(gnd + gna + na + 1);
-  for (uint64_t k = 0; k < gnd; ++k) stage[k] = uint32_t(G.dels[k]);
-  for (uint64_t k = 0; k < gna; ++k) stage[gnd + k] = uint32_t(G.addpos[k]);
-  for (uint64_t k = 0; k < na; ++k) stage[gnd + gna + k] = ag[k];
-  dbuf = PoolBuf(ctx->pool, stage.size() * 4);
-  if (!dbuf.p) return set_err(ctx, EMQX_GM_ENOMEM, "index_update: id map staging");
-  hipStream_t s = ctx->stream;
-  GM_HIP(ctx, hipMemcpyAsync(dbuf.p, stage.data(), stage.size() * 4, hipMemcpyHostToDevice, s));
-  const uint32_t* D = dbuf.as<uint32_t>();
-  const uint64_t g = std::min<uint64_t>(4096, (n_map + 255) / 256);
-  hipLaunchKernelGGL(k_gmap_shift, dim3(uint32_t(g)), dim3(256), 0, s, job.old_gmap, uint32_t(job.nb), uint32_t(na),
-                     rmap, D + gnd + gna, D, uint32_t(gnd), D + gnd, uint32_t(gna), job.new_gmap, uint32_t(job.n_new));
-  GM_HIP(ctx, hipGetLastError());
-  return EMQX_GM_OK;
-}
-}  // namespace
-
-int shift_gmap_device(emqx_gm_ctx* ctx, const GmapJob& job) {
-  std::vector<uint32_t> stage;
-  PoolBuf dbuf;
-  if (const int rc = queue_gmap_shift(ctx, job, nullptr, job.nb, stage, dbuf)) return rc;
-  GM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return EMQX_GM_OK;
-}
-
-int apply_patch_device(emqx_gm_ctx* ctx, void* dst, const void* src, size_t bytes,
-                       const std::vector<std::pair<uint64_t, uint32_t>>& ranges, const uint8_t* host,
-                       const IndexView& v, uint64_t o_hot, uint64_t o_nodes, uint64_t n_nodes,
-                       const IdShift& shift, const std::vector<std::pair<uint64_t, uint32_t>>& orops) {
-  return apply_patch_device_gmap(ctx, dst, src, bytes, ranges, host, v, o_hot, o_nodes, n_nodes, shift, orops, nullptr);
-}
-
-int apply_patch_device_gmap(emqx_gm_ctx* ctx, void* dst, const void* src, size_t bytes,
-                            const std::vector<std::pair<uint64_t, uint32_t>>& ranges, const uint8_t* host,
-                            const IndexView& v, uint64_t o_hot, uint64_t o_nodes, uint64_t n_nodes,
-                            const IdShift& shift, const std::vector<std::pair<uint64_t, uint32_t>>& orops,
-                            const GmapJob* gmap) {
-  uint64_t n_hot = 0;
-  for (int t = 0; t < HOT_TABLES; ++t) n_hot = std::max<uint64_t>(n_hot, v.hot_off[t] + v.hot_cap[t]);
-  const uint64_t hot_end = o_hot + n_hot * sizeof(HotSlot), nodes_end = o_nodes + n_nodes * sizeof(Node);
-  if (hot_end > bytes || nodes_end > bytes) return set_err(ctx, EMQX_GM_EINVAL, "index_update: tables outside the blob");
-  const bool unfused = knob("GM_UPDATE_UNFUSED") != nullptr;
-  // fused (one pass): the two id-bearing tables must not overlap
-  const bool fused = !unfused && (hot_end <= o_nodes || nodes_end <= o_hot);
-  // coalesce overlapping / adjacent ranges only (the bytes between two written
-  // fields may differ: the host mirror's untouched filter ids are stale), then
-  // cut into pieces
-  std::vector<std::pair<uint64_t, uint64_t>> seg;  // [begin, end)
-  {
-    std::vector<std::pair<uint64_t, uint32_t>> r(ranges);
-    std::sort(r.begin(), r.end());
-    for (const auto& x : r) {
-      if (!x.second) continue;
-      if (x.first + x.second > bytes) return set_err(ctx, EMQX_GM_EINVAL, "index_update: patch outside the blob");
-      if (!seg.empty() && x.first <= seg.back().second) seg.back().second = std::max(seg.back().second, x.first + x.second);
-      else seg.emplace_back(x.first, x.first + x.second);
-    }
-  }
-  for (const auto& o : orops)
-    if ((o.first & 3) || (o.first & ~PATCH_AND) + 4 > bytes)
-      return set_err(ctx, EMQX_GM_EINVAL, "index_update: OR/AND op outside the blob");
-  std::vector<uint64_t> desc;
-  uint64_t pay_n = 0;
-  for (const auto& g : seg) {
-    for (uint64_t b = g.first; b < g.second; b += PATCH_PIECE) {
-      const uint64_t n = std::min<uint64_t>(PATCH_PIECE, g.second - b);
-      desc.insert(desc.end(), {b, pay_n + (b - g.first), n});
-    }
-    pay_n += g.second - g.first;
-  }
-  const uint64_t n_pieces = desc.size() / 3;
-  if (n_pieces > 0x7FFFFFFFull) return set_err(ctx, EMQX_GM_EINVAL, "index_update: patch too large");
-  // staging: desc | payload | dels | addpos | OR ops (one upload); the id table after them (device-built)
-  const uint64_t nd = shift.dels.size(), na = shift.addpos.size(), n_map = shift.nb + na;
-  const size_t o_pay = (desc.size() * 8 + 255) & ~size_t(255);
-  const size_t o_dels = (o_pay + pay_n + 255) & ~size_t(255);
-  const size_t o_adds = (o_dels + nd * 4 + 4 + 255) & ~size_t(255);
-  const size_t o_ors = (o_adds + na * 4 + 4 + 255) & ~size_t(255);
-  const size_t up = o_ors + orops.size() * 16 + 16;
-  const size_t o_rmap = (up + 255) & ~size_t(255);
-  const size_t total = o_rmap + n_map * 4 + 4;
-  std::vector<uint8_t> st(up, 0);
-  if (!desc.empty()) std::memcpy(st.data(), desc.data(), desc.size() * 8);
-  {
-    uint64_t q = o_pay;
-    for (const auto& g : seg) {
-      uint8_t* const pb = st.data() + q;
-      std::memcpy(pb, host + g.first, g.second - g.first);
-      // fused: the range's filter ids (this update's temporary numbering) go up final
-      if (fused && !(renum_payload(pb, g.first, g.second, o_hot, n_hot, sizeof(HotSlot), kHotIds, shift, n_map) &&
-                     renum_payload(pb, g.first, g.second, o_nodes, n_nodes, sizeof(Node), kNodeIds, shift, n_map)))
-        return set_err(ctx, EMQX_GM_EINVAL, "index_update: a patched filter id outside the update's ids");
-      q += g.second - g.first;
-    }
-  }
-  for (uint64_t k = 0; k < nd; ++k) reinterpret_cast<uint32_t*>(st.data() + o_dels)[k] = uint32_t(shift.dels[k]);
-  for (uint64_t k = 0; k < na; ++k) reinterpret_cast<uint32_t*>(st.data() + o_adds)[k] = uint32_t(shift.addpos[k]);
-  for (size_t k = 0; k < orops.size(); ++k) {
-    const uint64_t w[2] = {orops[k].first, orops[k].second};
-    std::memcpy(st.data() + o_ors + 16 * k, w, 16);
-  }
-  PoolBuf dbuf(ctx->pool, total);
-  if (!dbuf.p) return set_err(ctx, EMQX_GM_ENOMEM, "index_update: staging buffer");
-  hipStream_t s = ctx->stream;
-  uint8_t* D = static_cast<uint8_t*>(dst);
-  const uint8_t* S = dbuf.as<uint8_t>();
-  uint32_t* const RM = reinterpret_cast<uint32_t*>(dbuf.as<uint8_t>() + o_rmap);
-  auto shift_table = [&]() -> int {
-    if (n_map) {
-      hipLaunchKernelGGL(k_shift_table, dim3(uint32_t((n_map + 255) / 256)), dim3(256), 0, s, RM, shift.nb,
-                         reinterpret_cast<const uint32_t*>(S + o_dels), uint32_t(nd),
-                         reinterpret_cast<const uint32_t*>(S + o_adds), uint32_t(na));
-      GM_HIP(ctx, hipGetLastError());
-    }
-    return 0;
-  };
-  const uint64_t g = std::min<uint64_t>(8192, (std::max(n_hot, n_nodes) + 255) / 256);
-  if (fused) {
-    GM_HIP(ctx, hipMemcpyAsync(dbuf.p, st.data(), up, hipMemcpyHostToDevice, s));
-    if (const int rc = shift_table()) return rc;
-    // the bytes around the two tables as they are, the tables renumbered on the way
-    const uint64_t a0 = std::min(o_hot, o_nodes), a1 = std::min(hot_end, nodes_end);
-    const uint64_t b0 = std::max(o_hot, o_nodes), b1 = std::max(hot_end, nodes_end);
-    const uint64_t gaps[3][2] = {{0, a0}, {a1, b0}, {b1, bytes}};
-    for (const auto& gp : gaps)
-      if (gp[1] > gp[0])
-        GM_HIP(ctx, hipMemcpyAsync(D + gp[0], static_cast<const uint8_t*>(src) + gp[0], gp[1] - gp[0],
-                                   hipMemcpyDeviceToDevice, s));
-    const uint8_t* SRC = static_cast<const uint8_t*>(src);
-    hipLaunchKernelGGL(k_renumber_copy, dim3(uint32_t(g ? g : 1)), dim3(256), 0, s,
-                       reinterpret_cast<const HotSlot*>(SRC + o_hot), reinterpret_cast<HotSlot*>(D + o_hot), n_hot,
-                       reinterpret_cast<const Node*>(SRC + o_nodes), reinterpret_cast<Node*>(D + o_nodes), n_nodes, RM);
-    GM_HIP(ctx, hipGetLastError());
-  } else {
-    GM_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
-    GM_HIP(ctx, hipMemcpyAsync(dbuf.p, st.data(), up, hipMemcpyHostToDevice, s));
-  }
-  if (n_pieces) {
-    hipLaunchKernelGGL(k_patch_scatter, dim3(uint32_t(n_pieces)), dim3(256), 0, s, D,
-                       reinterpret_cast<const uint64_t*>(S), S + o_pay);
-    GM_HIP(ctx, hipGetLastError());
-  }
-  if (!orops.empty()) {
-    hipLaunchKernelGGL(k_patch_or, dim3(uint32_t((orops.size() + 255) / 256)), dim3(256), 0, s,
-                       reinterpret_cast<uint32_t*>(D), reinterpret_cast<const uint64_t*>(S + o_ors),
-                       uint64_t(orops.size()));
-    GM_HIP(ctx, hipGetLastError());
-  }
-  if (!fused) {
-    if (const int rc = shift_table()) return rc;
-    hipLaunchKernelGGL(k_renumber, dim3(uint32_t(g ? g : 1)), dim3(256), 0, s, reinterpret_cast<HotSlot*>(D + o_hot),
-                       n_hot, reinterpret_cast<Node*>(D + o_nodes), n_nodes, RM);
-    GM_HIP(ctx, hipGetLastError());
-  }
-  // a shard's new id map, behind the patch on the same stream (it reads the shift's table)
-  std::vector<uint32_t> gm_stage;
-  PoolBuf gm_dbuf;
-  if (gmap)
-    if (const int rc = queue_gmap_shift(ctx, *gmap, RM, n_map, gm_stage, gm_dbuf)) {
-      (void)hipStreamSynchronize(s);
-      return rc;
-    }
-  GM_HIP(ctx, hipStreamSynchronize(s));  // the staging buffers go back to the pool / the host
-  return EMQX_GM_OK;
-}
-
-// ---- the new subscriber CSR of emqx_gm_index_update_subs (gm_subs.cpp) ----
-// Output element p of the new CSR belongs to filter f (the last segment whose
-// start <= p); its source is f's edited list from the host (f in aff_ids) or
-// element p - nsoff[f] of the previous list of f's old id inv[f].  Every
-// workgroup owns per_block consecutive outputs, as k_fanout_copy does.
-__device__ __forceinline__ uint64_t seg_of(const uint64_t* __restrict__ s, uint64_t a, uint64_t b, uint64_t p) {
-  // s[a] <= p < s[b]: the last segment of [a, b) starting at or before p
-  while (b - a > 1) {
-    const uint64_t m = (a + b) >> 1;
-    if (s[m] <= p) a = m;
-    else b = m;
-  }
-  return a;
-}
-__global__ __launch_bounds__(256) void k_subs_copy(const uint64_t* __restrict__ nsoff, uint64_t nf,
-                                                   const uint32_t* __restrict__ inv, const uint64_t* __restrict__ osoff,
-                                                   const uint32_t* __restrict__ oids, const uint32_t* __restrict__ aff_ids,
-                                                   uint64_t n_aff, const uint64_t* __restrict__ aff_off,
-                                                   const uint32_t* __restrict__ aff_buf, uint64_t total,
-                                                   uint64_t per_block, uint32_t* __restrict__ out) {
-  const uint64_t lo = uint64_t(blockIdx.x) * per_block;
-  if (lo >= total) return;
-  const uint64_t hi = min(total, lo + per_block);
-  __shared__ uint64_t s_seg[2];
-  if (threadIdx.x < 2) s_seg[threadIdx.x] = seg_of(nsoff, 0, nf, threadIdx.x == 0 ? lo : hi - 1);
-  __syncthreads();
-  const uint64_t s0 = s_seg[0], s1 = s_seg[1] + 1;
-  for (uint64_t p = lo + threadIdx.x; p < hi; p += 256) {
-    const uint64_t f = seg_of(nsoff, s0, s1, p);
-    const uint64_t q = p - nsoff[f];
-    uint64_t a = 0, b = n_aff;  // is f a touched filter?
-    while (a < b) {
-      const uint64_t m = (a + b) >> 1;
-      if (aff_ids[m] < f) a = m + 1;
-      else b = m;
-    }
-    out[p] = (a < n_aff && aff_ids[a] == f) ? aff_buf[aff_off[a] + q] : oids[osoff[inv ? inv[f] : f] + q];
-  }
-}
-
-// A subscriber-only batch (ids unchanged): new sub_off[i] = old sub_off[i] +
-// the count changes of the touched filters below i (tid ascending, tcum their
-// running sum) -- the host uploads only the touched ids
-__global__ __launch_bounds__(256) void k_soff_shift(const uint64_t* __restrict__ osoff, uint64_t n1,
-                                                    const uint32_t* __restrict__ tid, const int64_t* __restrict__ tcum,
-                                                    uint64_t nt, uint64_t* __restrict__ nsoff) {
-  for (uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x; i < n1; i += uint64_t(gridDim.x) * 256u) {
-    uint64_t a = 0, b = nt;  // touched ids below i
-    while (a < b) {
-      const uint64_t m = (a + b) >> 1;
-      if (tid[m] < i) a = m + 1;
-      else b = m;
-    }
-    nsoff[i] = uint64_t(int64_t(osoff[i]) + (a ? tcum[a - 1] : 0));
-  }
-}
-
-__global__ __launch_bounds__(256) void k_gather_segments(const uint32_t* __restrict__ src,
-                                                         const uint64_t* __restrict__ src_off,
-                                                         const uint64_t* __restrict__ dst_off, uint64_t m,
-                                                         uint64_t total, uint64_t per_block,
-                                                         uint32_t* __restrict__ out) {
-  const uint64_t lo = uint64_t(blockIdx.x) * per_block;
-  if (lo >= total) return;
-  const uint64_t hi = min(total, lo + per_block);
-  __shared__ uint64_t s_seg[2];
-  if (threadIdx.x < 2) s_seg[threadIdx.x] = seg_of(dst_off, 0, m, threadIdx.x == 0 ? lo : hi - 1);
-  __syncthreads();
-  const uint64_t s0 = s_seg[0], s1 = s_seg[1] + 1;
-  for (uint64_t p = lo + threadIdx.x; p < hi; p += 256) {
-    const uint64_t j = seg_of(dst_off, s0, s1, p);
-    out[p] = src[src_off[j] + (p - dst_off[j])];
-  }
-}
-
-int gather_segments(emqx_gm_ctx* ctx, const uint32_t* src, const std::vector<uint64_t>& src_off,
-                    const std::vector<uint64_t>& dst_off, uint32_t* out) {
-  const uint64_t m = src_off.size(), total = dst_off.back();
-  if (!total) return EMQX_GM_OK;
-  hipStream_t st = ctx->stream;
-  PoolBuf so(ctx->pool, m * 8 + 8), dof(ctx->pool, (m + 1) * 8), buf(ctx->pool, total * 4 + 16);
-  if (!so.p || !dof.p || !buf.p) return set_err(ctx, EMQX_GM_ENOMEM, "gather_segments: workspace");
-  GM_HIP(ctx, hipMemcpyAsync(so.p, src_off.data(), m * 8, hipMemcpyHostToDevice, st));
-  GM_HIP(ctx, hipMemcpyAsync(dof.p, dst_off.data(), (m + 1) * 8, hipMemcpyHostToDevice, st));
-  const uint64_t per = fan_per_block(total);
-  hipLaunchKernelGGL(k_gather_segments, dim3((total + per - 1) / per), dim3(256), 0, st, src, so.as<uint64_t>(),
-                     dof.as<uint64_t>(), m, total, per, buf.as<uint32_t>());
-  GM_HIP(ctx, hipGetLastError());
-  GM_HIP(ctx, hipMemcpyAsync(out, buf.p, total * 4, hipMemcpyDeviceToHost, st));
-  GM_HIP(ctx, hipStreamSynchronize(st));
-  return EMQX_GM_OK;
-}
-
-// The new subscriber CSR of a subscriber-only emqx_gm_index_update_subs batch
-// (gm_subs.cpp; filter ids unchanged): O(delta) host work -- the touched
-// filters' ids, count changes and lists go up -- and the device derives the
-// offsets (k_soff_shift) and copies every other filter's segment from prev's
-// CSR (k_subs_copy with the identity id map).
-int shift_subs_device(emqx_gm_ctx* ctx, const emqx_gm_index* prev, emqx_gm_index* idx,
-                      const std::vector<uint32_t>& aff_ids, const std::vector<uint64_t>& aff_off,
-                      const std::vector<uint32_t>& aff_buf) {
-  const uint64_t nf = prev->info.n_filters, na = aff_ids.size();
-  std::vector<int64_t> tcum(na + 1, 0);
-  int64_t cum = 0;
-  for (uint64_t k = 0; k < na; ++k) {
-    if (aff_ids[k] >= nf || (k && aff_ids[k] <= aff_ids[k - 1]))
-      return set_err(ctx, EMQX_GM_EINVAL, "index_update_subs: touched ids");
-    cum += int64_t(aff_off[k + 1] - aff_off[k]) - int64_t(prev->subs.count(aff_ids[k]));
-    tcum[k] = cum;
-  }
-  const uint64_t total = uint64_t(int64_t(prev->subs.total()) + cum);
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t o_ids = al((nf + 1) * 8);
-  GM_HIP(ctx, hipMalloc(&idx->dev_subs, o_ids + total * 4 + 16));
-  idx->subs_bytes = o_ids + total * 4 + 16;
-  uint8_t* D = static_cast<uint8_t*>(idx->dev_subs);
-  hipStream_t st = ctx->stream;
-  // staging: tid | tcum | aff_off | aff_buf
-  const size_t o_cum = al(na * 4 + 4), o_aoff = o_cum + al((na + 1) * 8), o_abuf = o_aoff + al(aff_off.size() * 8),
-               n_st = o_abuf + aff_buf.size() * 4 + 4;
-  std::vector<uint8_t> h(n_st, 0);
-  if (na) std::memcpy(h.data(), aff_ids.data(), na * 4);
-  std::memcpy(h.data() + o_cum, tcum.data(), (na + 1) * 8);
-  std::memcpy(h.data() + o_aoff, aff_off.data(), aff_off.size() * 8);
-  if (!aff_buf.empty()) std::memcpy(h.data() + o_abuf, aff_buf.data(), aff_buf.size() * 4);
-  PoolBuf sbuf(ctx->pool, n_st);
-  if (!sbuf.p) return set_err(ctx, EMQX_GM_ENOMEM, "index_update_subs: staging");
-  GM_HIP(ctx, hipMemcpyAsync(sbuf.p, h.data(), n_st, hipMemcpyHostToDevice, st));
-  const uint8_t* S = sbuf.as<uint8_t>();
-  const uint64_t g = std::min<uint64_t>(4096, (nf + 1 + 255) / 256);
-  hipLaunchKernelGGL(k_soff_shift, dim3(g), dim3(256), 0, st, prev->view.sub_off, nf + 1,
-                     reinterpret_cast<const uint32_t*>(S), reinterpret_cast<const int64_t*>(S + o_cum), na,
-                     reinterpret_cast<uint64_t*>(D));
-  GM_HIP(ctx, hipGetLastError());
-  if (total) {
-    const uint64_t per = fan_per_block(total);
-    hipLaunchKernelGGL(k_subs_copy, dim3((total + per - 1) / per), dim3(256), 0, st,
-                       reinterpret_cast<const uint64_t*>(D), nf, static_cast<const uint32_t*>(nullptr),
-                       prev->view.sub_off, prev->view.sub_ids, reinterpret_cast<const uint32_t*>(S), na,
-                       reinterpret_cast<const uint64_t*>(S + o_aoff), reinterpret_cast<const uint32_t*>(S + o_abuf),
-                       total, per, reinterpret_cast<uint32_t*>(D + o_ids));
-    GM_HIP(ctx, hipGetLastError());
-  }
-  GM_HIP(ctx, hipStreamSynchronize(st));  // the staging goes back to the pool / the host
-  idx->view.sub_off = reinterpret_cast<const uint64_t*>(D);
-  idx->view.sub_ids = reinterpret_cast<const uint32_t*>(D + o_ids);
-  idx->info.device_bytes += o_ids + total * 4 + 16;
-  return EMQX_GM_OK;
-}
-
-int rebuild_subs_device(emqx_gm_ctx* ctx, const emqx_gm_index* prev, emqx_gm_index* idx,
-                        const std::vector<uint64_t>& new_soff, const std::vector<uint32_t>& inv,
-                        const std::vector<uint32_t>& aff_ids, const std::vector<uint64_t>& aff_off,
-                        const std::vector<uint32_t>& aff_buf) {
-  const uint64_t nf = new_soff.size() - 1, total = new_soff.back();
-  for (uint64_t f = 0; f < nf; ++f)  // host-side check of what the kernel will index
-    if (inv[f] == NONE && !std::binary_search(aff_ids.begin(), aff_ids.end(), uint32_t(f)) &&
-        new_soff[f + 1] != new_soff[f])
-      return set_err(ctx, EMQX_GM_EINVAL, "index_update_subs: a new filter without its list");
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t o_ids = al((nf + 1) * 8);
-  GM_HIP(ctx, hipMalloc(&idx->dev_subs, o_ids + total * 4 + 16));
-  idx->subs_bytes = o_ids + total * 4 + 16;
-  uint8_t* D = static_cast<uint8_t*>(idx->dev_subs);
-  hipStream_t st = ctx->stream;
-  GM_HIP(ctx, hipMemcpyAsync(D, new_soff.data(), (nf + 1) * 8, hipMemcpyHostToDevice, st));
-  // staging: inv | aff_ids | aff_off | aff_buf
-  const size_t o_aid = al(nf * 4 + 4), o_aoff = o_aid + al(aff_ids.size() * 4 + 4),
-               o_abuf = o_aoff + al(aff_off.size() * 8), n_st = o_abuf + aff_buf.size() * 4 + 4;
-  std::vector<uint8_t> h(n_st, 0);
-  std::memcpy(h.data(), inv.data(), nf * 4);
-  if (!aff_ids.empty()) std::memcpy(h.data() + o_aid, aff_ids.data(), aff_ids.size() * 4);
-  std::memcpy(h.data() + o_aoff, aff_off.data(), aff_off.size() * 8);
-  if (!aff_buf.empty()) std::memcpy(h.data() + o_abuf, aff_buf.data(), aff_buf.size() * 4);
-  PoolBuf sbuf(ctx->pool, n_st);
-  if (!sbuf.p) return set_err(ctx, EMQX_GM_ENOMEM, "index_update_subs: staging");
-  GM_HIP(ctx, hipMemcpyAsync(sbuf.p, h.data(), n_st, hipMemcpyHostToDevice, st));
-  if (total) {
-    const uint8_t* S = sbuf.as<uint8_t>();
-    const uint64_t per = fan_per_block(total);
-    hipLaunchKernelGGL(k_subs_copy, dim3((total + per - 1) / per), dim3(256), 0, st,
-                       reinterpret_cast<const uint64_t*>(D), nf, reinterpret_cast<const uint32_t*>(S),
-                       prev->view.sub_off, prev->view.sub_ids, reinterpret_cast<const uint32_t*>(S + o_aid),
-                       uint64_t(aff_ids.size()), reinterpret_cast<const uint64_t*>(S + o_aoff),
-                       reinterpret_cast<const uint32_t*>(S + o_abuf), total, per,
-                       reinterpret_cast<uint32_t*>(D + o_ids));
-    GM_HIP(ctx, hipGetLastError());
-  }
-  GM_HIP(ctx, hipStreamSynchronize(st));  // the staging goes back to the pool / the host
-  idx->view.sub_off = reinterpret_cast<const uint64_t*>(D);
-  idx->view.sub_ids = reinterpret_cast<const uint32_t*>(D + o_ids);
-  idx->info.device_bytes += o_ids + total * 4 + 16;
-  return EMQX_GM_OK;
-}
-
-
-// ---------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------
-namespace {
-
 int finish_csr(emqx_gm_ctx* ctx, uint64_t n, uint64_t nnz, PoolBuf& row_off, PoolBuf& ids, bool device_out,
                emqx_gm_csr* out) {
   out->n_rows = n;
@@ -3484,6 +2418,8 @@ float ev_ms(hipEvent_t a, hipEvent_t b) {
   }
   return ms;
 }
+
+namespace {
 
 // Main-pass kernel selection.  GM_MATCH_MAIN (A/B knob, read per call so tests
 // cover every kind): fused (k_match_fused: tokenizer into registers + the
@@ -4313,312 +3249,6 @@ int refresh_d0(emqx_gm_ctx* ctx, const IndexView& v, void* d0) {
   GM_HIP(ctx, hipGetLastError());
   GM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
-}
-
-int scan_lengths(emqx_gm_ctx* ctx, const uint64_t* len, uint64_t n, uint64_t* out) {
-  return scan_excl(ctx, LoadU64{len}, n, out);
-}
-
-namespace {
-struct LoadU16 {
-  const uint16_t* p;
-  __device__ uint64_t operator()(uint64_t i) const { return p[i]; }
-};
-}  // namespace
-int scan_len16(emqx_gm_ctx* ctx, hipStream_t st, const uint16_t* len, uint64_t n, uint64_t* out) {
-  return scan_excl(ctx, LoadU16{len}, n, out, SideSum{}, nullptr, st);
-}
-
-int sum_filter_lengths(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint32_t* d_ids, uint64_t nnz,
-                       uint64_t* out) {
-  if (idx->flen_stale) {  // after an in-place update: the lengths in this snapshot's ids, once
-    std::lock_guard<std::mutex> lk(idx->flen_mu);
-    if (idx->flen_stale) {
-      const uint64_t nf = idx->info.n_filters;
-      std::vector<uint16_t> fl(nf + 1, 0);
-      idx->ft.for_each([&](uint64_t f, const uint8_t*, uint64_t l) { fl[f] = uint16_t(std::min<uint64_t>(l, 65535)); });
-      GM_HIP(ctx, hipMemcpyAsync(idx->dev_flen, fl.data(), nf * 2, hipMemcpyHostToDevice, ctx->stream));
-      GM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      idx->flen_stale = false;
-    }
-  }
-  PoolBuf acc(ctx->pool, 16);
-  if (!acc.p) return set_err(ctx, EMQX_GM_ENOMEM, "sum_flen");
-  GM_HIP(ctx, hipMemsetAsync(acc.p, 0, 8, ctx->stream));
-  if (nnz) {
-    const uint64_t blocks = std::min<uint64_t>(4096, (nnz + 255) / 256);
-    hipLaunchKernelGGL(k_sum_flen, dim3(blocks), dim3(256), 0, ctx->stream, d_ids, nnz, idx->dev_flen,
-                       idx->view.gmap, idx->view.n_filters, acc.as<unsigned long long>());
-    GM_HIP(ctx, hipGetLastError());
-  }
-  GM_HIP(ctx, hipMemcpyAsync(out, acc.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-  GM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return 0;
-}
-
-int run_fanout(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_csr* m, uint32_t flags,
-               emqx_gm_csr* out, uint32_t part, uint32_t n_parts, uint64_t* first_out) {
-  const bool dev_out = flags & EMQX_GM_DEVICE_IO;
-  hipStream_t st = ctx->stream;
-  const uint64_t n = m->n_rows, nnz = m->nnz;
-  ctx->stats = emqx_gm_match_stats{};
-  ctx->stats.n_topics = n;
-  PoolBuf own_off, own_ids;
-  const uint64_t* m_off = m->row_off;
-  const uint32_t* m_ids = m->ids;
-  if (!m->on_device) {
-    for (uint64_t i = 0; i < nnz; ++i)
-      if (m->ids[i] >= idx->view.n_filters) return set_err(ctx, EMQX_GM_EINVAL, "fanout: filter id out of range");
-    own_off = PoolBuf(ctx->pool, (n + 1) * 8);
-    own_ids = PoolBuf(ctx->pool, nnz * 4 + 16);
-    if (!own_off.p || !own_ids.p) return set_err(ctx, EMQX_GM_ENOMEM, "fanout: input workspace");
-    GM_HIP(ctx, hipMemcpyAsync(own_off.p, m->row_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
-    if (nnz) GM_HIP(ctx, hipMemcpyAsync(own_ids.p, m->ids, nnz * 4, hipMemcpyHostToDevice, st));
-    m_off = own_off.as<uint64_t>();
-    m_ids = own_ids.as<uint32_t>();
-  }
-  PoolBuf seg_dst(ctx->pool, (nnz + 1) * 8);
-  PoolBuf row_off(ctx->pool, (n + 1) * 8);
-  if (!seg_dst.p || !row_off.p) return set_err(ctx, EMQX_GM_ENOMEM, "fanout: workspace");
-  GM_HIP(ctx, hipEventRecord(ctx->ev[0], st));
-  int rc = scan_excl(ctx, LoadSegLen{m_ids, idx->view.sub_off}, nnz, seg_dst.as<uint64_t>());
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_fanout_rowoff, dim3((n + 1 + 255) / 256), dim3(256), 0, st, m_off, n, seg_dst.as<uint64_t>(),
-                     row_off.as<uint64_t>(), nnz);
-  GM_HIP(ctx, hipGetLastError());
-  uint64_t total = 0;
-  GM_HIP(ctx, hipMemcpyAsync(&total, seg_dst.as<uint64_t>() + nnz, 8, hipMemcpyDeviceToHost, st));
-  GM_HIP(ctx, hipStreamSynchronize(st));
-  // part `part` of n_parts: the contiguous delivery range [glo, ghi) of the
-  // whole fan-out (rows and wide rows alike are cut wherever the range ends)
-  // (the deliveries per match a small host fan-out sizes its speculative capacity by)
-  if (nnz) ctx->subs_per_match = std::max(1.0, double(total) / double(nnz));
-  const uint64_t glo = uint64_t((unsigned __int128)total * part / n_parts);
-  const uint64_t ghi = uint64_t((unsigned __int128)total * (part + 1) / n_parts);
-  const uint64_t cnt = ghi - glo;
-  if (first_out) *first_out = glo;
-  PoolBuf ids(ctx->pool, cnt * 4 + 16);
-  if (!ids.p) return set_err(ctx, EMQX_GM_ENOMEM, "fanout: output");
-  GM_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-  if (cnt) {
-    const uint64_t per = fan_per_block(cnt);
-    const uint64_t blocks = (cnt + per - 1) / per;
-    hipLaunchKernelGGL(k_fanout_copy, dim3(blocks), dim3(256), 0, st, seg_dst.as<uint64_t>(), nnz, m_ids,
-                       idx->view.sub_off, idx->view.sub_ids, glo, ghi, per, ids.as<uint32_t>(), false);
-    GM_HIP(ctx, hipGetLastError());
-  }
-  GM_HIP(ctx, hipEventRecord(ctx->ev[2], st));
-  GM_HIP(ctx, hipEventSynchronize(ctx->ev[2]));
-  ctx->stats.nnz = cnt;
-  ctx->stats.match_kernel_ms = ev_ms(ctx->ev[1], ctx->ev[2]);
-  ctx->stats.total_device_ms = ev_ms(ctx->ev[0], ctx->ev[2]);
-  return finish_csr(ctx, n, cnt, row_off, ids, dev_out, out);
-}
-
-// A small host fan-out's device work (gm_host.cpp run_fanout_small), queued
-// without a wait: the deliveries' offsets, the rows' offsets and the delivery
-// lists of [0, min(total, the device's count)) -- total: the call's capacity.
-int queue_fanout_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint64_t* d_off, const uint32_t* d_ids,
-                       uint64_t n, uint64_t nnz, uint64_t total, uint64_t* seg_dst, uint64_t* row_off, uint32_t* ids) {
-  hipStream_t st = ctx->stream;
-  if (nnz + 1 <= SCAN_LOOP_MAX) {
-    hipLaunchKernelGGL(k_scan_loop<LoadSegLen>, dim3(1), dim3(SCAN1_T), 0, st, LoadSegLen{d_ids, idx->view.sub_off},
-                       nnz, nnz + 1, seg_dst);
-    GM_HIP(ctx, hipGetLastError());
-  } else if (int rc = scan_excl(ctx, LoadSegLen{d_ids, idx->view.sub_off}, nnz, seg_dst)) {
-    return rc;
-  }
-  hipLaunchKernelGGL(k_fanout_rowoff, dim3((n + 1 + 255) / 256), dim3(256), 0, st, d_off, n, seg_dst, row_off, nnz);
-  GM_HIP(ctx, hipGetLastError());
-  if (total) {
-    const uint64_t per = fan_per_block(total);
-    hipLaunchKernelGGL(k_fanout_copy, dim3((total + per - 1) / per), dim3(256), 0, st, seg_dst, nnz, d_ids,
-                       idx->view.sub_off, idx->view.sub_ids, uint64_t(0), total, per, ids, true);
-    GM_HIP(ctx, hipGetLastError());
-  }
-  return 0;
-}
-
-// The fan-out of a small host call's speculative rows, queued right behind its
-// assembly (emqx_gm_match_fanout, gm_host.cpp run_host_small): d_ro/d_ids the
-// speculative CSR (cap_m ids), the deliveries into cap_f -- both counts checked
-// by the host after the call's one wait.
-int queue_fanout_spec(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint64_t* d_ro, const uint32_t* d_ids,
-                      uint64_t n, uint64_t cap_m, uint64_t cap_f, uint64_t* seg_dst, uint64_t* row_off, uint32_t* ids) {
-  hipStream_t st = ctx->stream;
-  const LoadSegLenSpec ld{d_ids, idx->view.sub_off, d_ro + n, uint32_t(idx->view.n_filters)};
-  if (cap_m + 1 <= SCAN_LOOP_MAX) {
-    hipLaunchKernelGGL(k_scan_loop<LoadSegLenSpec>, dim3(1), dim3(SCAN1_T), 0, st, ld, cap_m, cap_m + 1, seg_dst);
-    GM_HIP(ctx, hipGetLastError());
-  } else if (int rc = scan_excl(ctx, ld, cap_m, seg_dst)) {
-    return rc;
-  }
-  hipLaunchKernelGGL(k_fanout_rowoff, dim3((n + 1 + 255) / 256), dim3(256), 0, st, d_ro, n, seg_dst, row_off, cap_m);
-  GM_HIP(ctx, hipGetLastError());
-  const uint64_t per = fan_per_block(cap_f);
-  hipLaunchKernelGGL(k_fanout_copy, dim3((cap_f + per - 1) / per), dim3(256), 0, st, seg_dst, cap_m, d_ids,
-                     idx->view.sub_off, idx->view.sub_ids, uint64_t(0), cap_f, per, ids, true);
-  GM_HIP(ctx, hipGetLastError());
-  return 0;
-}
-
-// Rows back in their batch order after a prefix-routed exchange (sharded.py,
-// gm_route.hip): out row perm[i] = input row i, the input rows packed in send
-// order with u32 lengths lens[i].
-__global__ __launch_bounds__(256) void k_unperm_lens(const uint32_t* __restrict__ lens, const uint32_t* __restrict__ perm,
-                                                     uint64_t n, uint64_t* __restrict__ lens_out,
-                                                     uint64_t* __restrict__ lens_in, uint32_t* __restrict__ inv) {
-  const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
-  if (i < n) {
-    lens_out[perm[i]] = lens[i];
-    lens_in[i] = lens[i];
-    inv[perm[i]] = uint32_t(i);
-  }
-}
-// output row j = input row inv[j] (k_gather_segs, output-driven: one coalesced write)
-struct UnpermSeg {
-  const uint64_t* in_off;
-  const uint32_t* inv;
-  __device__ __forceinline__ SegSpan at(uint64_t j) const {
-    const uint64_t a = in_off[inv[j]];
-    return {a, in_off[inv[j] + 1] - a};
-  }
-};
-int unpermute_rows(emqx_gm_ctx* ctx, uint64_t n, const uint32_t* d_perm, const uint32_t* d_lens, const uint32_t* d_ids,
-                   uint32_t flags, emqx_gm_csr* out) {
-  hipStream_t st = ctx->stream;
-  PoolBuf row_off(ctx->pool, (n + 1) * 8), in_off(ctx->pool, (n + 1) * 8), l_out(ctx->pool, n * 8 + 8),
-      l_in(ctx->pool, n * 8 + 8), inv(ctx->pool, n * 4 + 4);
-  if (!row_off.p || !in_off.p || !l_out.p || !l_in.p || !inv.p)
-    return set_err(ctx, EMQX_GM_ENOMEM, "unpermute_rows: workspace");
-  if (n) {
-    hipLaunchKernelGGL(k_unperm_lens, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, st, d_lens, d_perm, n,
-                       l_out.as<uint64_t>(), l_in.as<uint64_t>(), inv.as<uint32_t>());
-    GM_HIP(ctx, hipGetLastError());
-  }
-  if (int rc = scan_lengths(ctx, l_out.as<uint64_t>(), n, row_off.as<uint64_t>())) return rc;
-  if (int rc = scan_lengths(ctx, l_in.as<uint64_t>(), n, in_off.as<uint64_t>())) return rc;
-  uint64_t nnz = 0;
-  GM_HIP(ctx, hipMemcpyAsync(&nnz, row_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-  GM_HIP(ctx, hipStreamSynchronize(st));
-  PoolBuf ids(ctx->pool, nnz * 4 + 16);
-  if (!ids.p) return set_err(ctx, EMQX_GM_ENOMEM, "unpermute_rows: ids");
-  if (n) {
-    hipLaunchKernelGGL((k_gather_segs<uint32_t, UnpermSeg>), dim3(gather_blocks(n)), dim3(256), 0, st, d_ids,
-                       UnpermSeg{in_off.as<uint64_t>(), inv.as<uint32_t>()}, n, row_off.as<uint64_t>(),
-                       ids.as<uint32_t>());
-    GM_HIP(ctx, hipGetLastError());
-  }
-  return finish_csr(ctx, n, nnz, row_off, ids, flags & EMQX_GM_DEVICE_IO, out);
-}
-
-int run_merge_rows(emqx_gm_ctx* ctx, uint64_t n, uint64_t stride, uint32_t pieces, const uint32_t* d_lens,
-                   const uint32_t* d_ids, uint32_t flags, emqx_gm_csr* out) {
-  hipStream_t st = ctx->stream;
-  ctx->stats = emqx_gm_match_stats{};
-  ctx->stats.n_topics = n;
-  const uint64_t nl = uint64_t(pieces) * stride;
-  PoolBuf pos(ctx->pool, (nl + 1) * 8), row_off(ctx->pool, (n + 1) * 8);
-  if (!pos.p || !row_off.p) return set_err(ctx, EMQX_GM_ENOMEM, "merge_rows: workspace");
-  GM_HIP(ctx, hipEventRecord(ctx->ev[0], st));
-  int rc = scan_excl(ctx, LoadU32{d_lens}, nl, pos.as<uint64_t>());
-  if (rc) return rc;
-  rc = scan_excl(ctx, LoadRowSum{d_lens, stride, pieces}, n, row_off.as<uint64_t>());
-  if (rc) return rc;
-  uint64_t nnz = 0;
-  GM_HIP(ctx, hipMemcpyAsync(&nnz, row_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-  GM_HIP(ctx, hipStreamSynchronize(st));
-  PoolBuf ids(ctx->pool, nnz * 4 + 16);
-  if (!ids.p) return set_err(ctx, EMQX_GM_ENOMEM, "merge_rows: output");
-  GM_HIP(ctx, hipEventRecord(ctx->ev[1], st));
-  if (n) {
-    hipLaunchKernelGGL(k_merge_rows, dim3((n + 255) / 256), dim3(256), 0, st, d_lens, pos.as<uint64_t>(), d_ids, n,
-                       stride, pieces, row_off.as<uint64_t>(), ids.as<uint32_t>());
-    GM_HIP(ctx, hipGetLastError());
-  }
-  GM_HIP(ctx, hipEventRecord(ctx->ev[2], st));
-  GM_HIP(ctx, hipEventSynchronize(ctx->ev[2]));
-  ctx->stats.nnz = nnz;
-  ctx->stats.match_kernel_ms = ev_ms(ctx->ev[1], ctx->ev[2]);
-  ctx->stats.total_device_ms = ev_ms(ctx->ev[0], ctx->ev[2]);
-  return finish_csr(ctx, n, nnz, row_off, ids, flags & EMQX_GM_DEVICE_IO, out);
-}
-
-int run_row_lengths(emqx_gm_ctx* ctx, const emqx_gm_csr* csr, uint32_t* d_out) {
-  if (csr->n_rows) {
-    hipLaunchKernelGGL(k_row_lengths, dim3((csr->n_rows + 255) / 256), dim3(256), 0, ctx->stream, csr->row_off,
-                       csr->n_rows, d_out);
-    GM_HIP(ctx, hipGetLastError());
-  }
-  GM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return 0;
-}
-
-// Match on an overlay snapshot: the base and the delta snapshots each match
-// the batch (inputs copied to the device once), then one pass drops
-// tombstoned base ids, remaps the survivors to final ids and merges the delta
-// row in (both rows sorted, disjoint).
-int run_match_overlay(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb_in, const uint64_t* to_in,
-                      uint64_t n, uint32_t flags, emqx_gm_csr* out) {
-  const OverlayState& ov = *idx->ov;
-  const bool dev_io = flags & EMQX_GM_DEVICE_IO;
-  hipStream_t st = ctx->stream;
-  PoolBuf d_tb_own, d_to_own;
-  const uint8_t* tb = tb_in;
-  const uint64_t* to = to_in;
-  if (!dev_io && n) {
-    const uint64_t bytes = to_in[n];
-    for (uint64_t i = 0; i < n; ++i)
-      if (to_in[i + 1] < to_in[i]) return set_err(ctx, EMQX_GM_EINVAL, "match: topic offsets not monotone");
-    d_tb_own = PoolBuf(ctx->pool, bytes + 64);
-    d_to_own = PoolBuf(ctx->pool, (n + 1) * 8);
-    if (!d_tb_own.p || !d_to_own.p) return set_err(ctx, EMQX_GM_ENOMEM, "match: input workspace");
-    if (bytes) GM_HIP(ctx, hipMemcpyAsync(d_tb_own.p, tb_in, bytes, hipMemcpyHostToDevice, st));
-    GM_HIP(ctx, hipMemsetAsync(static_cast<uint8_t*>(d_tb_own.p) + bytes, 0, 64, st));
-    GM_HIP(ctx, hipMemcpyAsync(d_to_own.p, to_in, (n + 1) * 8, hipMemcpyHostToDevice, st));
-    tb = d_tb_own.as<uint8_t>();
-    to = d_to_own.as<uint64_t>();
-  }
-  const uint32_t sub_flags = (flags & EMQX_GM_WITH_EXACT) | EMQX_GM_DEVICE_IO;
-  emqx_gm_csr cb{}, cd{};
-  int rc = run_match(ctx, ov.base, tb, to, n, sub_flags, &cb);
-  if (rc) return rc;
-  PoolBuf b_off, b_ids, d_off, d_ids;  // adopt the sub-results' pool buffers
-  b_off.pool = b_ids.pool = d_off.pool = d_ids.pool = ctx->pool;
-  b_off.p = cb.row_off;
-  b_ids.p = cb.ids;
-  emqx_gm_match_stats st_b = ctx->stats, st_d{};
-  if (ov.delta) {
-    rc = run_match(ctx, ov.delta, tb, to, n, sub_flags, &cd);
-    if (rc) return rc;
-    d_off.p = cd.row_off;
-    d_ids.p = cd.ids;
-    st_d = ctx->stats;
-  }
-  PoolBuf row_off(ctx->pool, (n + 1) * 8);
-  if (!row_off.p) return set_err(ctx, EMQX_GM_ENOMEM, "match: row_off");
-  const OvView o{ov.d_tbm, ov.d_tpre, ov.d_ins, uint32_t(ov.ins.size())};
-  rc = scan_excl(ctx, LoadOvLen{cb.row_off, cb.ids, ov.delta ? cd.row_off : nullptr, o}, n, row_off.as<uint64_t>());
-  if (rc) return rc;
-  uint64_t nnz = 0;
-  GM_HIP(ctx, hipMemcpyAsync(&nnz, row_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-  GM_HIP(ctx, hipStreamSynchronize(st));
-  PoolBuf ids(ctx->pool, nnz * 4 + 16);
-  if (!ids.p) return set_err(ctx, EMQX_GM_ENOMEM, "match: ids");
-  if (n) {
-    hipLaunchKernelGGL(k_ov_merge, dim3((n + 255) / 256), dim3(256), 0, st, cb.row_off, cb.ids,
-                       ov.delta ? cd.row_off : nullptr, ov.delta ? cd.ids : nullptr, o, n, row_off.as<uint64_t>(),
-                       ids.as<uint32_t>());
-    GM_HIP(ctx, hipGetLastError());
-  }
-  GM_HIP(ctx, hipStreamSynchronize(st));
-  ctx->stats = st_b;
-  ctx->stats.nnz = nnz;
-  ctx->stats.probes += st_d.probes;
-  ctx->stats.n_overflow += st_d.n_overflow;
-  ctx->stats.match_kernel_ms += st_d.match_kernel_ms;
-  ctx->stats.total_device_ms += st_d.total_device_ms;
-  return finish_csr(ctx, n, nnz, row_off, ids, dev_io, out);
 }
 
 }  // namespace gm

@@ -450,7 +450,7 @@ struct Patcher {
 };
 
 // rmap[temporary id] -> final id (NONE: deleted) over every filter-id field
-// (the host twin of gm_match.hip's k_renumber), split over a few threads
+// (the host twin of gm_update.hip's k_renumber), split over a few threads
 void renumber_host(Mirror& M, const IndexView& v, const std::vector<uint32_t>& rmap) {
   HotSlot* hot = reinterpret_cast<HotSlot*>(M.blob.data() + M.o_hot);
   Node* nd = reinterpret_cast<Node*>(M.blob.data() + M.o_nodes);
@@ -481,7 +481,7 @@ void renumber_host(Mirror& M, const IndexView& v, const std::vector<uint32_t>& r
 
 }  // namespace
 
-// (the device build defines it in gm_match.hip; the host-only ASAN build of
+// (the device build defines it in gm_update.hip; the host-only ASAN build of
 // this file links this stand-in: no shard index is patched without a device)
 __attribute__((weak)) int apply_patch_device_gmap(emqx_gm_ctx* ctx, void*, const void*, size_t,
                                                   const std::vector<std::pair<uint64_t, uint32_t>>&, const uint8_t*,

@@ -497,8 +497,6 @@ void free_route(emqx_gm_route* r) {
   delete r;
 }
 
-int scan_lengths(emqx_gm_ctx* ctx, const uint64_t* len, uint64_t n, uint64_t* out);
-
 int permute_topics(emqx_gm_ctx* ctx, const uint8_t* d_tb, const uint64_t* d_to, uint64_t n, const uint32_t* d_perm,
                    uint8_t* d_out, uint64_t* d_out_off) {
   if (!n) {

@@ -15,7 +15,7 @@
 //   * route changes (first subscriber / last one gone) go through the in-place
 //     trie patch (gm_overlay.cpp, patch_update);
 //   * the new snapshot gets a subscriber CSR of its own, written on the device
-//     (gm_match.hip, rebuild_subs_device): untouched filters' lists copied from
+//     (gm_update.hip, rebuild_subs_device): untouched filters' lists copied from
 //     the previous CSR through the id renumbering, touched ones from the host.
 // Anything the patch cannot take (no room, a filter with '#' inside, a
 // snapshot that is no longer the newest) rebuilds the index from the full

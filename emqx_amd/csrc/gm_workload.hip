@@ -99,15 +99,7 @@ __global__ __launch_bounds__(256) void k_topic_write(uint64_t seed, uint64_t sta
   }
 }
 
-struct LoadLen {
-  const uint64_t* p;
-  __device__ uint64_t operator()(uint64_t i) const { return p[i]; }
-};
-
 }  // namespace
-
-// scan helper from gm_match.hip
-int scan_lengths(emqx_gm_ctx* ctx, const uint64_t* len, uint64_t n, uint64_t* out);
 
 }  // namespace gm
 

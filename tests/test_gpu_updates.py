@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(params=["patch", "patch_mph", "patch_unfused", "overlay"])
 def form(request, monkeypatch):
     # patch_unfused: the device side as copy, patch, renumber in place (the A/B
-    # twin of the default one-pass copy-and-renumber, gm_match.hip apply_patch_device)
+    # twin of the default one-pass copy-and-renumber, gm_update.hip apply_patch_device)
     if request.param == "patch_unfused":
         monkeypatch.setenv("GM_UPDATE_UNFUSED", "1")
     else:
