@@ -123,6 +123,18 @@ class PublishStats(C.Structure):
                 ("n_pairs", C.c_uint64), ("cap_hits", C.c_uint64), ("cap_pairs", C.c_uint64)]
 
 
+class PublishWin(C.Structure):
+    _fields_ = [("w", Window), ("msg_hash", C.c_void_p)]
+
+
+class PublishGroupStats(C.Structure):
+    _fields_ = [("seq", C.c_uint64), ("position", C.c_uint32), ("n_windows", C.c_uint32),
+                ("device_waits", C.c_uint32), ("grouped", C.c_uint8), ("rows_spec", C.c_uint8),
+                ("picks_spec", C.c_uint8), ("forwards_spec", C.c_uint8), ("window_picks_exact", C.c_uint8),
+                ("window_forwards_exact", C.c_uint8), ("reserved8", C.c_uint8 * 6), ("cap_hits", C.c_uint64),
+                ("cap_pairs", C.c_uint64), ("n_hits", C.c_uint64), ("n_pairs", C.c_uint64)]
+
+
 class AuthzDesc(C.Structure):
     _fields_ = [("n_segments", C.c_uint32), ("seg_kind", C.c_void_p), ("seg_range_off", C.c_void_p),
                 ("n_ranges", C.c_uint64), ("range_rule_off", C.c_void_p), ("key_bytes", C.c_void_p),
@@ -219,6 +231,11 @@ SIGNATURES = {
     "emqx_gm_publish_window": (_i32, [_vp, _vp, _vp, _vp, _u64, C.POINTER(PublishOpts), C.POINTER(PublishResult),
                                       C.POINTER(PublishStats)]),
     "emqx_gm_publish_result_free": (_i32, [_vp, C.POINTER(PublishResult)]),
+    "emqx_gm_publish_windows": (_i32, [_vp, _vp, C.POINTER(PublishWin), _u32, C.POINTER(PublishOpts),
+                                       C.POINTER(PublishResult), C.POINTER(PublishStats),
+                                       C.POINTER(PublishGroupStats)]),
+    "emqx_gm_combiner_publish": (_i32, [_vp, _vp, _vp, _vp, _u64, C.POINTER(PublishOpts), C.POINTER(PublishResult),
+                                        C.POINTER(PublishStats), C.POINTER(PublishGroupStats)]),
     "emqx_gm_authz_build": (_i32, [_vp, C.POINTER(AuthzDesc), _u32, C.POINTER(_vp)]),
     "emqx_gm_authz_check": (_i32, [_vp, _vp, C.POINTER(AuthzBatch), _u32, _vp, _vp]),
     "emqx_gm_authz_info": (_i32, [_vp, C.POINTER(AuthzInfo)]),

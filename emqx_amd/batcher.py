@@ -198,7 +198,8 @@ class GpuRoutes:
         what its ``dispatch_batch`` gives, same per-call seed rule) and forward
         plan (``cluster``, a ClusterRoutes: what its ``plan`` gives) from ONE
         ``Context.publish_window`` call -- one device round trip where the three
-        calls make five waits.  Returns (rows, snapshot, (row_off, filter ids),
+        calls make five waits; with a combiner, ``Combiner.publish_window``: the
+        same call, coalesced with the whole windows of concurrent callers.  Returns (rows, snapshot, (row_off, filter ids),
         picks per row or None, ForwardPlan or None, stats)."""
         self.refresh()
         if self.stale:
@@ -206,7 +207,7 @@ class GpuRoutes:
         idx = self.index
         st = shared.table(idx) if shared is not None else None
         dt = cluster.table(idx) if cluster is not None else None
-        (ro, ids), (fro, fids), picks, plan, stats = self.ctx.publish_window(
+        (ro, ids), (fro, fids), picks, plan, stats = (self.combiner or self.ctx).publish_window(
             idx, list(topics), exact=True, shared=st, strategy=strategy, hashes=hashes,
             seed=shared.next_seed() if shared is not None else 0, dests=dt,
             skip_node=cluster.self_id if cluster is not None else None)
@@ -258,7 +259,10 @@ class PublishBatcher:
     ``one_call`` (needs ``routes``; used when ``shared`` or ``cluster`` is
     given): the window's rows, picks and plan come from ONE ``routes.window``
     call (emqx_gm_publish_window: one device round trip) instead of the three
-    calls above; the results are the same."""
+    calls above; the results are the same.  With ``routes`` built over a
+    combiner (``GpuRoutes(ctx, combiner=cb)``) that call goes through it
+    (emqx_gm_combiner_publish): whole windows of concurrent batchers share one
+    device round trip."""
 
     def __init__(self, groups_fn: Optional[Callable[[Sequence[bytes]], List[Row]]] = None, max_batch: int = 4096,
                  window_s: float = 0.001, subscribers: Optional[Dict[int, object]] = None,

@@ -2,6 +2,7 @@
 // No C++ exception crosses the ABI; every failure is an EMQX_GM_E* code with
 // the message in emqx_gm_last_error().
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -1031,6 +1032,12 @@ struct CombCall {
   emqx_gm_csr* deliveries = nullptr;
   emqx_gm_match_stats stats{};  // the group's
   std::string err;              // the leader's message, on failure
+  // a whole publish window (emqx_gm_combiner_publish): its hashes, opts and outputs
+  const uint32_t* msg_hash = nullptr;
+  emqx_gm_publish_opts popts{};
+  emqx_gm_publish_result* pres = nullptr;
+  emqx_gm_publish_stats pst{};
+  emqx_gm_publish_group_stats pgs{};
 };
 }  // namespace
 
@@ -1039,11 +1046,18 @@ struct emqx_gm_combiner {
   uint32_t max_windows = kGroupWindows;
   uint64_t max_topics = 0;
   gm::Combiner* q = nullptr;
+  // publish groups: their sequence numbers, and the lock that makes the numbers
+  // of groups with a stateful strategy the order in which they run
+  std::atomic<uint64_t> seq{0};
+  std::mutex order_mu;
   ~emqx_gm_combiner() { delete q; }
 };
 
+static int combiner_run_publish(emqx_gm_combiner* cb, gm::CombWindow* const* g, uint32_t n);
+
 // a group of the queue through match_windows_run: the leader's thread runs it
 static int combiner_run(emqx_gm_combiner* cb, gm::CombWindow* const* g, uint32_t n) {
+  if (g[0]->kind == 1) return combiner_run_publish(cb, g, n);
   emqx_gm_ctx* ctx = cb->ctx;
   const emqx_gm_index* idx = static_cast<const emqx_gm_index*>(g[0]->index);
   const bool fan = g[0]->want_deliveries;
@@ -1134,6 +1148,247 @@ int emqx_gm_combiner_match(emqx_gm_combiner* cb, const emqx_gm_index* idx, const
     return rc;
   }
   return gm::set_err(ctx, rc, c.err.empty() ? "combiner_match: the combiner is closed" : c.err);
+  GM_GUARD_END(ctx)
+}
+
+// ---- whole publish windows coalesced into one device round trip
+// (emqx_gm_publish_windows, emqx_gm_combiner_publish; gm_publish.hip's group
+// stage): the reference's unit of work, emqx_broker:publish/1 -> route/2 per
+// message from many publisher processes at once (apps/emqx/src/emqx_broker.erl:
+// 204-215, 245-293, 296-322; emqx_shared_sub.erl:113-130), for a node's whole
+// scheduler pool ----
+namespace {
+// what emqx_gm_publish_window checks of the opts and their tables, before any device work
+int publish_opts_check(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_publish_opts* o, const std::string& who) {
+  if (o->flags & ~EMQX_GM_WITH_EXACT) return gm::set_err(ctx, EMQX_GM_EINVAL, who + ": flags (host buffers only)");
+  if (idx->device != ctx->device) return gm::set_err(ctx, EMQX_GM_EINVAL, who + ": index lives on another device");
+  if (const emqx_gm_shared* sh = o->shared) {
+    if (o->strategy > EMQX_GM_SHARE_RANDOM) return gm::set_err(ctx, EMQX_GM_EINVAL, who + ": strategy");
+    if (!sh->dev_base) return gm::set_err(ctx, EMQX_GM_EUNSUPPORTED, who + ": a host-only shared table");
+    if (sh->device != ctx->device)
+      return gm::set_err(ctx, EMQX_GM_EINVAL, who + ": the shared table is on another device");
+    if (sh->idx != idx)
+      return gm::set_err(ctx, EMQX_GM_EINVAL, who + ": the shared table is bound to another snapshot");
+  }
+  if (const emqx_gm_dests* dt = o->dests) {
+    if (!dt->dev_base) return gm::set_err(ctx, EMQX_GM_EUNSUPPORTED, who + ": a host-only dests table");
+    if (dt->device != ctx->device)
+      return gm::set_err(ctx, EMQX_GM_EINVAL, who + ": the dests table is on another device");
+    if (dt->idx != idx)
+      return gm::set_err(ctx, EMQX_GM_EINVAL, who + ": the dests table is bound to another snapshot");
+  }
+  return EMQX_GM_OK;
+}
+
+// 0: bad (the message set), else window_kind's answer
+int publish_window_kind(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_publish_win& w,
+                        const emqx_gm_publish_opts* o, const std::string& who) {
+  if (w.w.n_topics && (!w.w.topic_bytes || !w.w.topic_off)) {
+    gm::set_err(ctx, EMQX_GM_EINVAL, who + ": NULL window");
+    return 0;
+  }
+  if (w.w.n_topics >= 0xFFFFFFF0ull) {
+    gm::set_err(ctx, EMQX_GM_EINVAL, who + ": batch too large (>= 2^32 topics)");
+    return 0;
+  }
+  if (o->shared && o->strategy == EMQX_GM_SHARE_HASH && w.w.n_topics && !w.msg_hash) {
+    gm::set_err(ctx, EMQX_GM_EINVAL, who + ": msg_hash is required for EMQX_GM_SHARE_HASH");
+    return 0;
+  }
+  const int kind = window_kind(idx, w.w, o->flags, true);
+  if (!kind) gm::set_err(ctx, EMQX_GM_EINVAL, who + ": topic offsets not monotone");
+  return kind;
+}
+
+// the windows in order: groups through the group stage on this context's own
+// device (the first listed: it holds the side tables), the others alone through
+// emqx_gm_publish_window, in their place; arguments checked by the caller.
+// seq numbers the groups (a window alone is a group of one); with `order` (a
+// combiner) a group with a stateful strategy holds it from taking its number
+// until it has run, so the numbers are the order of the groups on the table.
+int publish_windows_loop(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_publish_win* w, uint32_t nw,
+                         const std::vector<int>& kind, const emqx_gm_publish_opts* o, emqx_gm_publish_result* out,
+                         emqx_gm_publish_stats* st, emqx_gm_publish_group_stats* gs, uint32_t max_windows,
+                         uint64_t max_topics, std::atomic<uint64_t>* seq, std::mutex* order) {
+  int rc = EMQX_GM_OK;
+  GM_GUARD_BEGIN
+  const bool stateful =
+      o->shared && (o->strategy == EMQX_GM_SHARE_ROUND_ROBIN || o->strategy == EMQX_GM_SHARE_STICKY);
+  std::vector<uint8_t> ok;
+  for (uint32_t k = 0; k < nw && rc == EMQX_GM_OK;) {
+    std::unique_lock<std::mutex> ol;
+    if (order && stateful) ol = std::unique_lock<std::mutex>(*order);
+    const uint64_t sq = seq->fetch_add(1, std::memory_order_relaxed);
+    if (kind[k] != 2) {
+      emqx_gm_publish_opts o1 = *o;
+      o1.msg_hash = w[k].msg_hash;
+      rc = emqx_gm_publish_window(ctx, idx, w[k].w.topic_bytes, w[k].w.topic_off, w[k].w.n_topics, &o1, &out[k], &st[k]);
+      emqx_gm_publish_group_stats q{};
+      q.seq = sq;
+      q.n_windows = 1;
+      q.device_waits = st[k].device_waits;
+      q.rows_spec = st[k].rows_spec;
+      q.picks_spec = st[k].picks_spec;
+      q.forwards_spec = st[k].forwards_spec;
+      q.cap_hits = st[k].cap_hits;
+      q.cap_pairs = st[k].cap_pairs;
+      q.n_hits = st[k].n_hits;
+      q.n_pairs = st[k].n_pairs;
+      gs[k] = q;
+      ++k;
+      continue;
+    }
+    uint32_t e = k;
+    uint64_t topics = 0, bytes = 0;
+    for (; e < nw && e - k < max_windows && kind[e] == 2; ++e) {
+      const uint64_t nb = w[e].w.n_topics ? w[e].w.topic_off[w[e].w.n_topics] - w[e].w.topic_off[0] : 0;
+      if (e > k && (topics + w[e].w.n_topics > max_topics || bytes + nb > gm::host_window_text_max())) break;
+      topics += w[e].w.n_topics;
+      bytes += nb;
+    }
+    gm::PwArgs a;
+    a.sh = o->shared;
+    a.strategy = o->strategy;
+    a.seed = o->seed;
+    a.dt = o->dests;
+    a.skip_node = o->skip_node;
+    ok.assign(e - k, 0);
+    emqx_gm_match_stats ms{};
+    hipSetDevice(ctx->device);
+    rc = gm::run_publish_windows(ctx, idx, w + k, e - k, o->flags, a, out + k, st + k, gs + k, ok.data(), &ms);
+    if (rc == EMQX_GM_OK) {
+      tl_stats = ms;
+      tl_stats_ctx = ctx;
+    }
+    for (uint32_t j = k; j < e && rc == EMQX_GM_OK; ++j) {
+      gs[j].seq = sq;
+      if (ok[j - k]) continue;
+      // (a window whose deliveries did not hold: emqx_gm_match_fanout's rule, the fan-out of its rows)
+      rc = emqx_gm_fanout(ctx, idx, &out[j].matches, 0, &out[j].deliveries);
+      st[j].device_waits += 1;
+    }
+    k = e;
+  }
+  return rc;
+  GM_GUARD_END(ctx)
+}
+
+// ... and on any failure (an exception included) every output is zeroed and nothing is held
+int publish_windows_run(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_publish_win* w, uint32_t nw,
+                        const std::vector<int>& kind, const emqx_gm_publish_opts* o, emqx_gm_publish_result* out,
+                        emqx_gm_publish_stats* st, emqx_gm_publish_group_stats* gs, uint32_t max_windows,
+                        uint64_t max_topics, std::atomic<uint64_t>* seq, std::mutex* order) {
+  for (uint32_t k = 0; k < nw; ++k) {
+    std::memset(&out[k], 0, sizeof(out[k]));
+    st[k] = emqx_gm_publish_stats{};
+    gs[k] = emqx_gm_publish_group_stats{};
+  }
+  const int rc = publish_windows_loop(ctx, idx, w, nw, kind, o, out, st, gs, max_windows, max_topics, seq, order);
+  if (rc != EMQX_GM_OK)
+    for (uint32_t k = 0; k < nw; ++k) emqx_gm_publish_result_free(ctx, &out[k]);
+  return rc;
+}
+}  // namespace
+
+int emqx_gm_publish_windows(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_publish_win* w, uint32_t nw,
+                            const emqx_gm_publish_opts* o, emqx_gm_publish_result* out, emqx_gm_publish_stats* stats,
+                            emqx_gm_publish_group_stats* gstats) {
+  if (!ctx) return EMQX_GM_EINVAL;
+  // every argument checked before any device work, no output touched
+  if (!idx || !o || (nw && (!w || !out))) return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_windows: NULL argument");
+  if (o->msg_hash)
+    return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_windows: opts->msg_hash must be NULL (each window brings its own)");
+  std::vector<int> kind;
+  std::vector<emqx_gm_publish_stats> st;
+  std::vector<emqx_gm_publish_group_stats> gs;
+  GM_GUARD_BEGIN
+  if (const int rc = publish_opts_check(ctx, idx, o, "publish_windows")) return rc;
+  kind.resize(nw);
+  for (uint32_t k = 0; k < nw; ++k)
+    if (!(kind[k] = publish_window_kind(ctx, idx, w[k], o, "publish_windows"))) return EMQX_GM_EINVAL;
+  if (!stats) st.resize(nw);
+  if (!gstats) gs.resize(nw);
+  GM_GUARD_END(ctx)
+  std::atomic<uint64_t> seq{0};
+  return publish_windows_run(ctx, idx, w, nw, kind, o, out, stats ? stats : st.data(), gstats ? gstats : gs.data(),
+                             kGroupWindows, gm::host_chunk_topics(), &seq, nullptr);
+}
+
+// a group of publish windows of the queue through publish_windows_run: the leader's thread runs it
+static int combiner_run_publish(emqx_gm_combiner* cb, gm::CombWindow* const* g, uint32_t n) {
+  emqx_gm_ctx* ctx = cb->ctx;
+  const emqx_gm_index* idx = static_cast<const emqx_gm_index*>(g[0]->index);
+  std::vector<emqx_gm_publish_win> w(n);
+  std::vector<int> kind(n);
+  std::vector<emqx_gm_publish_result> res(n);
+  std::vector<emqx_gm_publish_stats> st(n);
+  std::vector<emqx_gm_publish_group_stats> gs(n);
+  for (uint32_t k = 0; k < n; ++k) {
+    const CombCall* c = static_cast<const CombCall*>(g[k]->user);
+    w[k].w = c->win;
+    w[k].msg_hash = c->msg_hash;
+    kind[k] = c->kind;
+  }
+  emqx_gm_publish_opts o = static_cast<const CombCall*>(g[0]->user)->popts;  // (the group's key: every member's are these)
+  o.msg_hash = nullptr;
+  const int rc = publish_windows_run(ctx, idx, w.data(), n, kind, &o, res.data(), st.data(), gs.data(), cb->max_windows,
+                                     cb->max_topics, &cb->seq, &cb->order_mu);
+  const char* msg = rc != EMQX_GM_OK ? emqx_gm_last_error(ctx) : nullptr;
+  for (uint32_t k = 0; k < n; ++k) {
+    CombCall* c = static_cast<CombCall*>(g[k]->user);
+    g[k]->rc = rc;
+    if (rc == EMQX_GM_OK) {
+      *c->pres = res[k];
+      c->pst = st[k];
+      c->pgs = gs[k];
+      c->stats = tl_stats;
+    } else if (msg) {
+      c->err = msg;
+    }
+  }
+  return 0;
+}
+
+int emqx_gm_combiner_publish(emqx_gm_combiner* cb, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to,
+                             uint64_t n, const emqx_gm_publish_opts* o, emqx_gm_publish_result* out,
+                             emqx_gm_publish_stats* stats, emqx_gm_publish_group_stats* where) {
+  if (!cb) return EMQX_GM_EINVAL;
+  emqx_gm_ctx* ctx = cb->ctx;
+  // the caller's own window checked here: a bad one fails this call alone, no output touched
+  if (!idx || !o || !out || (n && (!tb || !to)))
+    return gm::set_err(ctx, EMQX_GM_EINVAL, "combiner_publish: NULL argument");
+  GM_GUARD_BEGIN
+  if (const int rc = publish_opts_check(ctx, idx, o, "combiner_publish")) return rc;
+  CombCall c;
+  c.win = emqx_gm_window{tb, to, n};
+  c.msg_hash = o->msg_hash;
+  c.popts = *o;
+  c.pres = out;
+  const emqx_gm_publish_win pw{c.win, c.msg_hash};
+  if (!(c.kind = publish_window_kind(ctx, idx, pw, o, "combiner_publish"))) return EMQX_GM_EINVAL;
+  std::memset(out, 0, sizeof(*out));
+  gm::CombWindow qw;
+  qw.index = idx;
+  qw.flags = o->flags;
+  qw.want_deliveries = true;
+  qw.kind = 1;
+  qw.shared = o->shared;
+  qw.dests = o->dests;
+  qw.strategy = o->shared ? o->strategy : 0;
+  qw.seed = o->shared ? o->seed : 0;
+  qw.skip_node = o->dests ? o->skip_node : 0;
+  qw.n_topics = n;
+  qw.n_bytes = n ? to[n] - to[0] : 0;
+  qw.user = &c;
+  const int rc = cb->q->submit(&qw);
+  if (rc == EMQX_GM_OK) {
+    if (stats) *stats = c.pst;
+    if (where) *where = c.pgs;
+    tl_stats = c.stats;
+    tl_stats_ctx = ctx;
+    return rc;
+  }
+  return gm::set_err(ctx, rc, c.err.empty() ? "combiner_publish: the combiner is closed" : c.err);
   GM_GUARD_END(ctx)
 }
 

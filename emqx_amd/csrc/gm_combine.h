@@ -7,7 +7,7 @@
 // Policy: a caller enqueues its window; while fewer than max_in_flight groups
 // are out, a queued caller becomes a leader: it takes its own window and, in
 // arrival order, every queued window compatible with it (same key: index,
-// flags, deliveries or not) up to max_windows windows, max_topics topics and
+// flags, deliveries or not, call kind and a publish window's opts) up to max_windows windows, max_topics topics and
 // max_bytes of text, runs them, and hands every member its return code.
 // Incompatible or surplus windows stay queued; when a group comes back, the
 // waiters are woken and the first still-queued one leads the next group.  With
@@ -37,6 +37,12 @@ struct CombWindow {
   const void* index = nullptr;
   uint32_t flags = 0;
   bool want_deliveries = false;
+  // ... of a whole publish window (emqx_gm_combiner_publish): the call kind and the opts every
+  // window of a group shares (defaulted: a match window's key is what it was)
+  uint32_t kind = 0;  // 0: match / match + fan-out, 1: publish window
+  const void* shared = nullptr;
+  const void* dests = nullptr;
+  uint32_t strategy = 0, seed = 0, skip_node = 0;
   // size, for the group limits
   uint64_t n_topics = 0;
   uint64_t n_bytes = 0;
@@ -113,7 +119,9 @@ class Combiner {
 
  private:
   static bool compatible(const CombWindow* a, const CombWindow* b) {
-    return a->index == b->index && a->flags == b->flags && a->want_deliveries == b->want_deliveries;
+    return a->index == b->index && a->flags == b->flags && a->want_deliveries == b->want_deliveries &&
+           a->kind == b->kind && a->shared == b->shared && a->dests == b->dests && a->strategy == b->strategy &&
+           a->seed == b->seed && a->skip_node == b->skip_node;
   }
 
   bool gathering_for(const CombWindow* w) const {

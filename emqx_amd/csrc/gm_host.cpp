@@ -1039,7 +1039,8 @@ int run_host_small(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb
 uint64_t host_window_text_max() { return kMappedMax; }
 
 int run_host_windows(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_window* w, uint32_t g, uint32_t flags,
-                     emqx_gm_csr* matches, emqx_gm_csr* deliveries, uint8_t* fan_ok, emqx_gm_match_stats* st_out) {
+                     emqx_gm_csr* matches, emqx_gm_csr* deliveries, uint8_t* fan_ok, emqx_gm_match_stats* st_out,
+                     WindowsSide* side) {
   const int nc = deliveries ? 2 : 1;  // the CSRs per window: matches, deliveries
   uint64_t n = 0, nbytes = 0;
   for (uint32_t k = 0; k < g; ++k) {
@@ -1102,10 +1103,11 @@ int run_host_windows(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_w
     return 0;
   }
   // ---- outside the lock: the group staged in a page-locked buffer of its own:
-  // [the windows' text | 64 B of zeros | their u16 lengths | the window table]
+  // [the windows' text | 64 B of zeros | their u16 lengths | the window table | the side stage's room]
   const size_t o_len = (nbytes + 64 + 255) & ~size_t(255);
   const size_t o_tab = al16(o_len + n * 2 + 2);
-  const size_t in_bytes = al16(o_tab + size_t(g) * 2 * sizeof(WinSlice));
+  const size_t o_side = al16(o_tab + size_t(g) * 2 * sizeof(WinSlice));
+  const size_t in_bytes = al16(o_side + (side ? side->extra_bytes : 0));
   PinBuf pin(ctx->pins);
   if (!(pin.p = ctx->pins->get(in_bytes))) return set_err(ctx, EMQX_GM_ENOMEM, "match_windows: pinned staging");
   uint8_t* in = static_cast<uint8_t*>(pin.p);
@@ -1122,6 +1124,7 @@ int run_host_windows(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_w
     }
     std::memset(in + nbytes, 0, 64);
   }
+  if (side && side->stage) side->stage(in + o_side);
   WinSlice* tab = reinterpret_cast<WinSlice*>(in + o_tab);
   auto dev_of = [](void* h) {  // a page-locked buffer as the device addresses it
     void* d = nullptr;
@@ -1183,6 +1186,7 @@ int run_host_windows(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_w
   const uint8_t* d_b = static_cast<const uint8_t*>(dv[0]);
   const WinSlice* d_tab = reinterpret_cast<const WinSlice*>(d_b + o_tab);
   uint64_t* d_o = static_cast<uint64_t*>(dv[1]);
+  if (side && side->prepare) side->prepare(in + o_side, d_b + o_side);  // (its tables: up with the same copy)
   if (launch_copy_u32x2(st, static_cast<const uint32_t*>(in_dev), static_cast<uint32_t*>(dv[0]), in_bytes / 4, nullptr,
                         nullptr, 0) ||
       scan_len16(ctx, st, reinterpret_cast<const uint16_t*>(d_b + o_len), n, d_o)) {
@@ -1208,6 +1212,7 @@ int run_host_windows(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_w
     if (launch_rows_split(st, d_tab, g, max_work, d_ro, d_ids, cap, fan_q ? static_cast<const uint64_t*>(fd[1]) : nullptr,
                           static_cast<const uint32_t*>(fd[2]), cap_fg))
       return set_err(ctx, EMQX_GM_EDEVICE, "match_windows: rows to host");
+    if (side) side->queue(d_ro, d_ids, cap);  // (the caller's stage: behind the rows and the fan-out)
     return 0;
   };
   void* ticket = nullptr;
@@ -1283,6 +1288,18 @@ int run_host_windows(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_w
     if (x == hipSuccess) x = y;
   }
   if (fan_held && dc.nnz) ctx->subs_per_match = std::max(1.0, double(f0) / double(dc.nnz));
+  if (side && x == hipSuccess) {  // the caller's stage made whole: the true rows and the side's tables still on the device
+    dc.n_rows = n;
+    dc.on_device = 1;
+    if (const int src = side->finish(tail.used, &dc)) {
+      drop_dev();
+      ctx->pool->release(dc.row_off);
+      ctx->pool->release(dc.ids);
+      drop_res();
+      for (uint32_t k = 0; k < g && deliveries; ++k) fan_ok[k] = 0;
+      return src;
+    }
+  }
   drop_dev();
   ctx->pool->release(dc.row_off);
   ctx->pool->release(dc.ids);

@@ -657,10 +657,44 @@ struct WinSlice {  // one window's part of one of the group's CSRs (the window t
 };
 int launch_rows_split(hipStream_t st, const WinSlice* tab, uint32_t n_windows, uint64_t max_work, const uint64_t* ro0,
                       const uint32_t* ids0, uint64_t cap0, const uint64_t* ro1, const uint32_t* ids1, uint64_t cap1);
+// The cut of a group's forward plan into the windows' own (gm_windows.hip
+// k_plan_bounds, k_plan_cut; emqx_gm_publish_windows).  tab[w]: window w's rows
+// in the group and its result as the device addresses it; win_row0: the
+// windows' first rows, n_windows + 1 ascending entries; lb: (n_windows + 1) x
+// n_nodes u32 of workspace, written when `bounds` (a relaunch for one window
+// passes tab + w, lb + w * n_nodes and bounds = false).  node_off / rows /
+// filters / row_routes: the group's plan within cap_pairs entries; *total_p,
+// the group's true pair count, is copied to *total_out.
+struct PlanSlice {
+  uint64_t row0, n_rows;   // its rows in the group
+  uint64_t pairs_cap;      // pairs its result holds
+  uint64_t* dst_node_off;  // n_nodes + 1 offsets from 0 (the last: its true pair count)
+  uint32_t *dst_rows, *dst_filters, *dst_row_routes;
+};
+int launch_plan_cut(hipStream_t st, const PlanSlice* tab, uint32_t n_windows, uint64_t max_work,
+                    const uint32_t* win_row0, uint32_t* lb, bool bounds, const uint64_t* node_off, const uint32_t* rows,
+                    const uint32_t* filters, const uint32_t* row_routes, uint32_t n_nodes, uint64_t cap_pairs,
+                    const uint64_t* total_p, uint64_t* total_out);
 uint64_t host_window_text_max();
 void free_combiners(emqx_gm_ctx* ctx);  // gm_api.cpp: closes and frees the context's combiners (emqx_gm_close)
+// side (optional, emqx_gm_publish_windows): the group analogue of SmallSide.
+// extra_bytes of room behind the group's staged input travel up with the same
+// copy: stage(host) fills what is known outside the lock (the windows' hashes);
+// prepare(host, dev) runs under ctx->mu before the input copy is queued (the
+// windows' tables: their capacities come from the context's state).  queue()
+// runs from the match's tail behind the group's speculative rows and fan-out,
+// finish() after the wait, under the lock, while the true device rows are held;
+// a finish() that fails fails the group.  A group without a topic calls none.
+struct WindowsSide {
+  size_t extra_bytes = 0;
+  std::function<void(uint8_t* host)> stage;
+  std::function<void(uint8_t* host, const uint8_t* dev)> prepare;
+  std::function<void(const uint64_t* row_off, const uint32_t* ids, uint64_t cap)> queue;
+  std::function<int(bool rows_spec, const emqx_gm_csr* rows)> finish;
+};
 int run_host_windows(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_window* w, uint32_t g, uint32_t flags,
-                     emqx_gm_csr* matches, emqx_gm_csr* deliveries, uint8_t* fan_ok, emqx_gm_match_stats* st_out);
+                     emqx_gm_csr* matches, emqx_gm_csr* deliveries, uint8_t* fan_ok, emqx_gm_match_stats* st_out,
+                     WindowsSide* side = nullptr);
 // gm_multi.cpp: multi-device contexts (emqx_gm_opts.n_devices).
 // A copy of flat snapshot `src` (any device) on member context m's device:
 // the host tables shared or copied, the device tables copied device to device

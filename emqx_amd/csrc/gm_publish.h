@@ -23,4 +23,16 @@ int run_publish_window(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t
                        uint32_t flags, const PwArgs& a, emqx_gm_publish_result* res, emqx_gm_publish_stats* st_out,
                        emqx_gm_match_stats* mst, SmallFan* fan);
 
+// A GROUP of such windows as one device batch (emqx_gm_publish_windows; entered
+// WITHOUT ctx->mu; the caller has checked what run_host_windows asks for): one
+// match, one fan-out, one pick stage and one plan stage over the group's rows
+// (a.msg_hash is not read: the windows bring their own), each result cut into
+// the windows' own.  res[k].deliveries is set where fan_ok[k] (else the caller
+// fans that window's rows out); st_out[k] / gst[k] are window k's figures (the
+// caller sets gst[k].seq).  On an error nothing is held and the shared table's
+// state is unchanged.
+int run_publish_windows(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_publish_win* w, uint32_t g,
+                        uint32_t flags, const PwArgs& a, emqx_gm_publish_result* res, emqx_gm_publish_stats* st_out,
+                        emqx_gm_publish_group_stats* gst, uint8_t* fan_ok, emqx_gm_match_stats* mst);
+
 }  // namespace gm

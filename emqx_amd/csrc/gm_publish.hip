@@ -25,10 +25,16 @@
 //           rows (sh_pick_device / dt_plan_device, host_out).
 // Capacities: the fan-out's rule -- 1024 + the ids past the slack x this
 // context's recent hits (pairs) per match, rounded up to a power of two.
+//
+// emqx_gm_publish_windows runs a GROUP of such windows as one batch (the
+// reference's many publisher processes at once, emqx_broker.erl:296-322): the
+// same two stages ONCE over the group's rows, then a cut into each window's own
+// result (PwGroupStage below; the cut's kernels: gm_windows.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
 #include "gm_dests.h"
 #include "gm_publish.h"
@@ -331,7 +337,476 @@ struct PwStage {
   }
 };
 
+// ---- the group stage (emqx_gm_publish_windows): PwStage for a group of windows
+// run as one batch (gm_host.cpp run_host_windows, WindowsSide).
+// stage()    outside the lock: the windows' hashes, concatenated in window
+//            order, and their first rows into the side's room behind the
+//            group's staged text (up with the group's one input copy).
+// prepare()  under the lock: each window's own capacities (spec_cap's rule on
+//            the window's rows capacity), its page-locked results, and the two
+//            window tables (picks: WinSlice x 2, plan: PlanSlice).
+// queue()    sh_queue_spec / dt_queue_spec ONCE over the group's rows and
+//            capacity (random: with the first-row table), then the cut:
+//            k_rows_split over the two pick CSRs (one shared row_off), and
+//            k_plan_bounds + k_plan_cut (gm_windows.hip).
+// finish()   the plan first, then the picks, the commit last.  A part the group
+//            held: a window past its own capacity gets a result of exact size
+//            (the plan's cut relaunched for it, the picks copied from the
+//            group's arrays), one more wait for all of them.  A part it did
+//            not hold: the exact call over the group's true device rows, its
+//            host result cut per window on the host by the same rule.
+struct PwGroupStage {
+  emqx_gm_ctx* ctx;
+  const PwArgs& a;
+  const emqx_gm_publish_win* w;
+  uint32_t g;
+  uint64_t n = 0;
+  uint32_t N = 0;
+  bool hash = false;
+  std::vector<uint32_t> row0;  // [g + 1]
+  size_t o_row0 = 0, o_ptab = 0, o_ftab = 0, extra = 0;  // (the hashes at 0)
+  uint8_t* h_x = nullptr;
+  const uint8_t* d_x = nullptr;
+  struct Win {
+    uint64_t n = 0;
+    uint64_t* p_off[2] = {nullptr, nullptr};
+    uint32_t* p_ids[2] = {nullptr, nullptr};
+    size_t p_ib = 0;  // bytes of each p_ids[]
+    uint64_t cap_hits = 0, hits = 0;
+    bool p_exact = false;
+    uint64_t* f_noff = nullptr;
+    uint32_t *f_rows = nullptr, *f_fil = nullptr, *f_rr = nullptr;
+    size_t f_ib = 0;  // bytes of f_rows / f_fil
+    uint64_t cap_pairs = 0, pairs = 0;
+    bool f_exact = false;
+  };
+  std::vector<Win> win;
+  bool tabs_pick = false, tabs_plan = false, q_pick = false, q_plan = false;
+  bool held_pick = false, held_plan = false, rows_spec = false;
+  ShSpec ps;
+  DtSpec fs;
+  uint32_t* d_lb = nullptr;
+  uint64_t* h_meta = nullptr;
+  uint64_t cap_hits = 0, cap_pairs = 0, hits_g = 0, pairs_g = 0, work_p = 0, work_f = 0;
+  uint32_t waits = 0;
+
+  PwGroupStage(emqx_gm_ctx* c, const PwArgs& args, const emqx_gm_publish_win* wins, uint32_t n_win)
+      : ctx(c), a(args), w(wins), g(n_win), row0(size_t(n_win) + 1, 0), win(n_win) {
+    for (uint32_t k = 0; k < g; ++k) {
+      win[k].n = w[k].w.n_topics;
+      row0[k] = uint32_t(n);
+      n += win[k].n;
+    }
+    row0[g] = uint32_t(n);
+    N = a.dt ? a.dt->hv.n_nodes : 0;
+    hash = a.sh && a.strategy == EMQX_GM_SHARE_HASH;
+    o_row0 = hash ? al16(n * 4) : 0;
+    o_ptab = al16(o_row0 + (size_t(g) + 1) * 4);
+    o_ftab = al16(o_ptab + size_t(g) * 2 * sizeof(WinSlice));
+    extra = al16(o_ftab + size_t(g) * sizeof(PlanSlice));
+  }
+
+  bool stateful() const {
+    return a.sh && (a.strategy == EMQX_GM_SHARE_ROUND_ROBIN || a.strategy == EMQX_GM_SHARE_STICKY);
+  }
+  const uint32_t* d_row0() const { return reinterpret_cast<const uint32_t*>(d_x + o_row0); }
+
+  void stage(uint8_t* host) {
+    if (hash)
+      for (uint32_t k = 0; k < g; ++k)
+        if (win[k].n) std::memcpy(host + size_t(row0[k]) * 4, w[k].msg_hash, win[k].n * 4);
+    std::memcpy(host + o_row0, row0.data(), (size_t(g) + 1) * 4);
+  }
+
+  // (all below under ctx->mu)
+  void drop_pick(Win& x) {
+    for (int c = 0; c < 2; ++c) {
+      ctx->hpool->release(x.p_off[c]);
+      ctx->hpool->release(x.p_ids[c]);
+      x.p_off[c] = nullptr;
+      x.p_ids[c] = nullptr;
+    }
+    x.p_ib = 0;
+  }
+  void drop_plan(Win& x) {
+    for (void* p : {static_cast<void*>(x.f_noff), static_cast<void*>(x.f_rows), static_cast<void*>(x.f_fil),
+                    static_cast<void*>(x.f_rr)})
+      ctx->hpool->release(p);
+    x.f_noff = nullptr;
+    x.f_rows = x.f_fil = x.f_rr = nullptr;
+    x.f_ib = 0;
+  }
+  void drop_device() {  // the workspaces back to the pool behind the work queued so far
+    void* ps3[3] = {ps.ws, fs.ws, d_lb};
+    for (void* p : ps3)
+      if (p) ctx->pool->release_after(p, ctx->stream);
+    ps = ShSpec{};
+    fs = DtSpec{};
+    d_lb = nullptr;
+    ctx->hpool->release(h_meta);
+    h_meta = nullptr;
+  }
+  void drop_all() {  // a failed group: nothing is held
+    drop_device();
+    for (Win& x : win) {
+      drop_pick(x);
+      drop_plan(x);
+    }
+  }
+
+  void prepare(uint8_t* host, const uint8_t* dev) {
+    h_x = host;
+    d_x = dev;
+    WinSlice* ptab = reinterpret_cast<WinSlice*>(host + o_ptab);
+    PlanSlice* ftab = reinterpret_cast<PlanSlice*>(host + o_ftab);
+    std::memset(host + o_ptab, 0, extra - o_ptab);
+    const double ipt = std::min(ctx->ids_per_topic, double(FAST_MC));
+    tabs_pick = a.sh != nullptr;
+    tabs_plan = a.dt != nullptr && N != 0;
+    for (uint32_t k = 0; k < g; ++k) {
+      Win& x = win[k];
+      const uint64_t cap_rows = 1024 + uint64_t(double(x.n) * ipt);  // (run_host_windows' rule for the window's ids)
+      if (tabs_pick) {
+        x.cap_hits = spec_cap(nullptr, cap_rows, ctx->hits_per_match);
+        x.p_ib = pow2_bytes(x.cap_hits);
+        for (int c = 0; c < 2 && x.cap_hits; ++c) {
+          x.p_off[c] = static_cast<uint64_t*>(ctx->hpool->alloc((x.n + 1) * 8, true));
+          x.p_ids[c] = static_cast<uint32_t*>(ctx->hpool->alloc(x.p_ib, true));
+          ptab[k * 2 + c] = WinSlice{row0[k], x.n, x.cap_hits, dev_ptr(x.p_off[c]), dev_ptr(x.p_ids[c])};
+          if (!ptab[k * 2 + c].dst_row_off || !ptab[k * 2 + c].dst_ids) tabs_pick = false;
+        }
+        if (!x.cap_hits) tabs_pick = false;
+        work_p = std::max({work_p, x.n + 1, (x.cap_hits + 3) / 4});
+      }
+      if (tabs_plan) {
+        x.cap_pairs = spec_cap(nullptr, cap_rows, ctx->pairs_per_match);
+        x.f_ib = pow2_bytes(x.cap_pairs);
+        if (x.cap_pairs) {
+          x.f_noff = static_cast<uint64_t*>(ctx->hpool->alloc((uint64_t(N) + 1) * 8, true));
+          x.f_rows = static_cast<uint32_t*>(ctx->hpool->alloc(x.f_ib, true));
+          x.f_fil = static_cast<uint32_t*>(ctx->hpool->alloc(x.f_ib, true));
+          x.f_rr = static_cast<uint32_t*>(ctx->hpool->alloc(std::max<size_t>(x.n * 4, 16), true));
+          ftab[k] = PlanSlice{row0[k],          x.n,
+                              x.cap_pairs,      dev_ptr(x.f_noff),
+                              dev_ptr(x.f_rows), dev_ptr(x.f_fil),
+                              dev_ptr(x.f_rr)};
+          if (!ftab[k].dst_node_off || !ftab[k].dst_rows || !ftab[k].dst_filters || !ftab[k].dst_row_routes)
+            tabs_plan = false;
+        } else {
+          tabs_plan = false;
+        }
+        work_f = std::max({work_f, (x.cap_pairs + 3) / 4, (x.n + 3) / 4});
+      }
+    }
+    // (no room for a part's results: nothing of it is queued, it runs after the wait)
+    if (!tabs_pick)
+      for (Win& x : win) drop_pick(x);
+    if (!tabs_plan)
+      for (Win& x : win) drop_plan(x);
+  }
+
+  void queue(const uint64_t* d_ro, const uint32_t* d_ids, uint64_t cap) {
+    hipStream_t s = ctx->stream;
+    if (tabs_pick && (cap_hits = spec_cap(knob("GM_PW_CAP_HITS"), cap, ctx->hits_per_match))) {
+      const uint32_t* d_hash = hash ? reinterpret_cast<const uint32_t*>(d_x) : nullptr;
+      q_pick = sh_queue_spec(ctx, a.sh, d_ro, d_ids, n, cap, cap_hits, a.strategy, d_hash, a.seed, &ps, d_row0(), g) == 0;
+      // the two pick CSRs share one row_off: k_rows_split's two planes, members and slots
+      if (q_pick && launch_rows_split(s, reinterpret_cast<const WinSlice*>(d_x + o_ptab), g, work_p, ps.row_off,
+                                      ps.members, cap_hits, ps.row_off, ps.slots, cap_hits))
+        q_pick = false;
+    }
+    if (tabs_plan && (cap_pairs = spec_cap(knob("GM_PW_CAP_PAIRS"), cap, ctx->pairs_per_match))) {
+      q_plan = dt_queue_spec(ctx, a.dt, d_ro, d_ids, n, cap, cap_pairs, a.skip_node, &fs) == 0;
+      if (q_plan) {
+        d_lb = static_cast<uint32_t*>(ctx->pool->alloc((size_t(g) + 1) * N * 4));
+        h_meta = static_cast<uint64_t*>(ctx->hpool->alloc(64, true));
+        uint64_t* meta = dev_ptr(h_meta);
+        if (!d_lb || !meta ||
+            launch_plan_cut(s, reinterpret_cast<const PlanSlice*>(d_x + o_ftab), g, work_f, d_row0(), d_lb, true,
+                            fs.node_off, fs.rows, fs.filters, fs.row_routes, N, cap_pairs, fs.total, meta))
+          q_plan = false;
+      }
+    }
+  }
+
+  // a window's pick ids again with room for `hits` (not mapped: filled by a copy or on the host)
+  bool pick_room(Win& x, uint64_t hits) {
+    for (int c = 0; c < 2; ++c)
+      if (!x.p_off[c] && !(x.p_off[c] = static_cast<uint64_t*>(ctx->hpool->alloc((x.n + 1) * 8)))) return false;
+    if (x.p_ids[0] && hits * 4 + 4 <= x.p_ib) return true;
+    for (int c = 0; c < 2; ++c) {
+      ctx->hpool->release(x.p_ids[c]);
+      x.p_ids[c] = static_cast<uint32_t*>(ctx->hpool->alloc(hits * 4 + 16));
+    }
+    x.p_ib = hits * 4 + 16;
+    return x.p_ids[0] && x.p_ids[1];
+  }
+  bool plan_room(Win& x, uint64_t pairs, bool mapped) {
+    if (!x.f_noff && !(x.f_noff = static_cast<uint64_t*>(ctx->hpool->alloc((uint64_t(N) + 1) * 8)))) return false;
+    if (!x.f_rr && !(x.f_rr = static_cast<uint32_t*>(ctx->hpool->alloc(std::max<size_t>(x.n * 4, 16))))) return false;
+    if (x.f_rows && pairs * 4 + 4 <= x.f_ib) return true;
+    ctx->hpool->release(x.f_rows);
+    ctx->hpool->release(x.f_fil);
+    x.f_ib = mapped ? pow2_bytes(pairs) : pairs * 4 + 16;
+    x.f_rows = static_cast<uint32_t*>(ctx->hpool->alloc(x.f_ib, mapped));
+    x.f_fil = static_cast<uint32_t*>(ctx->hpool->alloc(x.f_ib, mapped));
+    return x.f_rows && x.f_fil;
+  }
+
+  int finish_plan(const emqx_gm_csr* rows) {
+    pairs_g = h_meta ? h_meta[0] : 0;
+    held_plan = q_plan && rows_spec && pairs_g <= cap_pairs;
+    if (held_plan) {
+      bool again = false;
+      for (uint32_t k = 0; k < g; ++k) {
+        Win& x = win[k];
+        x.pairs = x.f_noff[N];
+        if (x.pairs <= x.cap_pairs) continue;
+        // this window alone past its own capacity: a result of exact size, its cut relaunched into it
+        x.f_exact = true;
+        if (!plan_room(x, x.pairs, true)) return set_err(ctx, EMQX_GM_ENOMEM, "publish_windows: host result");
+        PlanSlice* ft = reinterpret_cast<PlanSlice*>(h_x + o_ftab) + k;
+        ft->pairs_cap = x.pairs;
+        ft->dst_rows = dev_ptr(x.f_rows);
+        ft->dst_filters = dev_ptr(x.f_fil);
+        const PlanSlice* d_ft = reinterpret_cast<const PlanSlice*>(d_x + o_ftab) + k;
+        if (!ft->dst_rows || !ft->dst_filters ||
+            hipMemcpyAsync(const_cast<PlanSlice*>(d_ft), ft, sizeof(PlanSlice), hipMemcpyHostToDevice, ctx->stream) !=
+                hipSuccess ||
+            launch_plan_cut(ctx->stream, d_ft, 1, (x.pairs + 3) / 4, d_row0(), d_lb + size_t(k) * N, false, fs.node_off,
+                            fs.rows, fs.filters, fs.row_routes, N, cap_pairs, fs.total, dev_ptr(h_meta)))
+          return set_err(ctx, EMQX_GM_EDEVICE, "publish_windows: a window's plan again");
+        again = true;
+      }
+      if (again) {
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess)
+          return set_err(ctx, EMQX_GM_EDEVICE, "publish_windows: a window's plan again");
+        ++waits;
+      }
+      return EMQX_GM_OK;
+    }
+    // the group's plan at its exact size on the true device rows, cut on the host by the same rule
+    if (q_plan && hipStreamSynchronize(ctx->stream) != hipSuccess)  // (nothing queued still writes the windows' results)
+      return set_err(ctx, EMQX_GM_EDEVICE, "publish_windows: device");
+    emqx_gm_forwards gf{};
+    if (const int rc = dt_plan_device(ctx, a.dt, rows, a.skip_node, 0, &gf, true, &waits)) return rc;
+    pairs_g = gf.n_pairs;
+    int rc = EMQX_GM_OK;
+    std::vector<uint64_t> lb((size_t(g) + 1) * N);
+    for (uint32_t k = 0; k < N; ++k) {
+      const uint32_t* lo = gf.rows + gf.node_off[k];
+      const uint32_t* hi = gf.rows + gf.node_off[k + 1];
+      for (uint32_t b = 0; b <= g; ++b) lb[size_t(b) * N + k] = uint64_t(std::lower_bound(lo, hi, row0[b]) - lo);
+    }
+    for (uint32_t wk = 0; wk < g && rc == EMQX_GM_OK; ++wk) {
+      Win& x = win[wk];
+      const uint64_t *l0 = lb.data() + size_t(wk) * N, *l1 = l0 + N;
+      x.pairs = 0;
+      for (uint32_t k = 0; k < N; ++k) x.pairs += l1[k] - l0[k];
+      if (!plan_room(x, x.pairs, false)) {
+        rc = set_err(ctx, EMQX_GM_ENOMEM, "publish_windows: host result");
+        break;
+      }
+      uint64_t at = 0;
+      for (uint32_t k = 0; k < N; ++k) {
+        x.f_noff[k] = at;
+        const uint64_t src = gf.node_off[k] + l0[k], cnt = l1[k] - l0[k];
+        for (uint64_t i = 0; i < cnt; ++i) x.f_rows[at + i] = gf.rows[src + i] - row0[wk];
+        if (cnt) std::memcpy(x.f_fil + at, gf.filters + src, cnt * 4);
+        at += cnt;
+      }
+      x.f_noff[N] = at;
+      if (x.n) std::memcpy(x.f_rr, gf.row_routes + row0[wk], x.n * 4);
+    }
+    for (void* p : {static_cast<void*>(gf.node_off), static_cast<void*>(gf.rows), static_cast<void*>(gf.filters),
+                    static_cast<void*>(gf.row_routes)})
+      ctx->hpool->release(p);
+    return rc;
+  }
+
+  int finish_picks(const emqx_gm_csr* rows) {
+    hits_g = 0;
+    if (q_pick && rows_spec)
+      for (Win& x : win) hits_g += (x.hits = x.p_off[0][x.n]);
+    held_pick = q_pick && rows_spec && hits_g <= cap_hits;
+    if (held_pick) {
+      bool again = false;
+      uint64_t base = 0;
+      for (Win& x : win) {
+        if (x.hits > x.cap_hits) {  // this window alone past its own capacity: its ids from the group's arrays
+          x.p_exact = true;
+          if (!pick_room(x, x.hits)) return set_err(ctx, EMQX_GM_ENOMEM, "publish_windows: host result");
+          if (hipMemcpyAsync(x.p_ids[0], ps.members + base, x.hits * 4, hipMemcpyDeviceToHost, ctx->stream) !=
+                  hipSuccess ||
+              hipMemcpyAsync(x.p_ids[1], ps.slots + base, x.hits * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+            return set_err(ctx, EMQX_GM_EDEVICE, "publish_windows: a window's picks again");
+          again = true;
+        }
+        base += x.hits;
+      }
+      if (again) {
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess)
+          return set_err(ctx, EMQX_GM_EDEVICE, "publish_windows: a window's picks again");
+        ++waits;
+      }
+      // (queued under sh->mu: no wait of its own; ONE commit for the group)
+      return hits_g ? sh_queue_commit(ctx, a.sh, ps) : EMQX_GM_OK;
+    }
+    // the group's picks at their exact size on the true device rows (the call writes the table's state itself)
+    if (q_pick && hipStreamSynchronize(ctx->stream) != hipSuccess)
+      return set_err(ctx, EMQX_GM_EDEVICE, "publish_windows: device");
+    emqx_gm_csr gm{}, gsl{};
+    if (const int rc = sh_pick_device(ctx, a.sh, rows, a.strategy, hash ? reinterpret_cast<const uint32_t*>(h_x) : nullptr,
+                                      a.seed, 0, &gm, &gsl, true, &waits, d_row0(), g))
+      return rc;
+    hits_g = gm.nnz;
+    int rc = EMQX_GM_OK;
+    for (uint32_t k = 0; k < g; ++k) {
+      Win& x = win[k];
+      const uint64_t* ro = gm.row_off + row0[k];
+      x.hits = ro[x.n] - ro[0];
+      if (!pick_room(x, x.hits)) {
+        rc = set_err(ctx, EMQX_GM_ENOMEM, "publish_windows: host result");
+        break;
+      }
+      for (int c = 0; c < 2; ++c) {
+        for (uint64_t i = 0; i <= x.n; ++i) x.p_off[c][i] = ro[i] - ro[0];
+        if (x.hits) std::memcpy(x.p_ids[c], (c ? gsl.ids : gm.ids) + ro[0], x.hits * 4);
+      }
+    }
+    for (emqx_gm_csr* c : {&gm, &gsl}) {
+      ctx->hpool->release(c->row_off);
+      ctx->hpool->release(c->ids);
+    }
+    return rc;
+  }
+
+  int finish(bool spec, const emqx_gm_csr* rows) {
+    rows_spec = spec;
+    // the plan first: the picks' commit is the only step that changes state, and it comes last
+    if (a.dt) {
+      if (const int rc = finish_plan(rows)) return rc;
+      if (rows_spec && rows->nnz) ctx->pairs_per_match = std::max(1.0 / 64, double(pairs_g) / double(rows->nnz));
+    }
+    if (a.sh) {
+      if (const int rc = finish_picks(rows)) return rc;
+      if (rows_spec && rows->nnz) ctx->hits_per_match = std::max(1.0 / 64, double(hits_g) / double(rows->nnz));
+    }
+    drop_device();
+    return EMQX_GM_OK;
+  }
+
+  // a group without a topic: every window's empty side results, no device work
+  int empty() {
+    for (Win& x : win) {
+      if (a.sh) {
+        if (!pick_room(x, 0)) return set_err(ctx, EMQX_GM_ENOMEM, "publish_windows: host result");
+        x.p_off[0][0] = x.p_off[1][0] = 0;
+      }
+      if (a.dt) {
+        if (!plan_room(x, 0, false)) return set_err(ctx, EMQX_GM_ENOMEM, "publish_windows: host result");
+        std::fill(x.f_noff, x.f_noff + N + 1, uint64_t(0));
+      }
+    }
+    return EMQX_GM_OK;
+  }
+};
+
 }  // namespace
+
+int run_publish_windows(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_gm_publish_win* w, uint32_t g,
+                        uint32_t flags, const PwArgs& a, emqx_gm_publish_result* res, emqx_gm_publish_stats* st_out,
+                        emqx_gm_publish_group_stats* gst, uint8_t* fan_ok, emqx_gm_match_stats* mst) {
+  std::vector<emqx_gm_window> mw(g);
+  for (uint32_t k = 0; k < g; ++k) mw[k] = w[k].w;
+  std::vector<emqx_gm_csr> m(g), d(g);
+  PwGroupStage stage(ctx, a, w, g);
+  const bool sides = a.sh || a.dt;
+  WindowsSide side;
+  side.extra_bytes = stage.extra;
+  side.stage = [&](uint8_t* host) { stage.stage(host); };
+  side.prepare = [&](uint8_t* host, const uint8_t* dev) { stage.prepare(host, dev); };
+  side.queue = [&](const uint64_t* d_ro, const uint32_t* d_ids, uint64_t cap) { stage.queue(d_ro, d_ids, cap); };
+  side.finish = [&](bool rows_spec, const emqx_gm_csr* rows) { return stage.finish(rows_spec, rows); };
+  // the table's own serialisation, ONCE for the group, from the moment the stage
+  // is queued until the commit is queued (as run_publish_window's for a window)
+  std::unique_lock<std::mutex> tl;
+  if (stage.stateful()) tl = std::unique_lock<std::mutex>(a.sh->mu);
+  int rc = run_host_windows(ctx, idx, mw.data(), g, flags, m.data(), d.data(), fan_ok, mst, sides ? &side : nullptr);
+  if (rc == EMQX_GM_OK && sides && stage.n == 0) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    rc = stage.empty();
+  }
+  if (rc) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (stage.q_pick || stage.q_plan) hipStreamSynchronize(ctx->stream);  // (a queued kernel may still write the results)
+    stage.drop_all();
+    for (uint32_t k = 0; k < g; ++k) {
+      ctx->hpool->release(m[k].row_off);
+      ctx->hpool->release(m[k].ids);
+      ctx->hpool->release(d[k].row_off);
+      ctx->hpool->release(d[k].ids);
+    }
+    return rc;
+  }
+  tl = std::unique_lock<std::mutex>();
+  // the group's round trip; rows past their capacity: their copy
+  const uint32_t waits = stage.n ? stage.waits + 1 + (stage.rows_spec ? 0 : 1) : 0;
+  for (uint32_t k = 0; k < g; ++k) {
+    const PwGroupStage::Win& x = stage.win[k];
+    res[k] = emqx_gm_publish_result{};
+    res[k].matches = m[k];
+    if (fan_ok[k]) res[k].deliveries = d[k];
+    emqx_gm_publish_stats s{};
+    emqx_gm_publish_group_stats q{};
+    s.device_waits = q.device_waits = waits;
+    s.rows_spec = q.rows_spec = stage.rows_spec;
+    s.fanout_spec = fan_ok[k];
+    q.position = k;
+    q.n_windows = g;
+    q.grouped = 1;
+    if (a.sh) {
+      emqx_gm_csr* outs[2] = {&res[k].pick_members, &res[k].pick_slots};
+      for (int c = 0; c < 2; ++c) {
+        outs[c]->n_rows = x.n;
+        outs[c]->nnz = x.hits;
+        outs[c]->row_off = x.p_off[c];
+        outs[c]->ids = x.p_ids[c];
+        outs[c]->on_device = 0;
+        outs[c]->priv = ctx;
+      }
+      q.picks_spec = stage.held_pick;
+      q.window_picks_exact = x.p_exact;
+      s.picks_spec = stage.held_pick && !x.p_exact;
+      s.n_hits = x.hits;
+      s.cap_hits = x.cap_hits;
+      q.cap_hits = stage.cap_hits;
+      q.n_hits = stage.hits_g;
+    }
+    if (a.dt) {
+      emqx_gm_forwards& fw = res[k].forwards;
+      fw.n_rows = x.n;
+      fw.n_pairs = x.pairs;
+      fw.node_off = x.f_noff;
+      fw.rows = x.f_rows;
+      fw.filters = x.f_fil;
+      fw.row_routes = x.f_rr;
+      fw.n_nodes = stage.N;
+      fw.on_device = 0;
+      fw.priv = ctx;
+      q.forwards_spec = stage.held_plan;
+      q.window_forwards_exact = x.f_exact;
+      s.forwards_spec = stage.held_plan && !x.f_exact;
+      s.n_pairs = x.pairs;
+      s.cap_pairs = x.cap_pairs;
+      q.cap_pairs = stage.cap_pairs;
+      q.n_pairs = stage.pairs_g;
+    }
+    st_out[k] = s;
+    gst[k] = q;
+  }
+  return EMQX_GM_OK;
+}
 
 int run_publish_window(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to, uint64_t n,
                        uint32_t flags, const PwArgs& a, emqx_gm_publish_result* res, emqx_gm_publish_stats* st_out,

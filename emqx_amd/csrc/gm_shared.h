@@ -114,9 +114,13 @@ void sh_free_device(emqx_gm_shared* sh);
 int sh_read_state(emqx_gm_ctx* ctx, const emqx_gm_shared* sh, std::vector<uint32_t>& rr, std::vector<uint32_t>& st);
 // host_out: device rows in, but msg_hash and the result on the host (a publish
 // window's rerun); waits (optional): += the host-blocking device waits made
+// d_win_row0 (optional, device; a group of publish windows): the windows' first
+// rows, n_win ascending entries -- EMQX_GM_SHARE_RANDOM then mixes a message's
+// row in its own window, as a call on that window alone does
 int sh_pick_device(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, uint32_t strategy,
                    const uint32_t* msg_hash, uint32_t seed, uint32_t n_chunks, emqx_gm_csr* out_members,
-                   emqx_gm_csr* out_slots, bool host_out = false, uint32_t* waits = nullptr);
+                   emqx_gm_csr* out_slots, bool host_out = false, uint32_t* waits = nullptr,
+                   const uint32_t* d_win_row0 = nullptr, uint32_t n_win = 0);
 // A pick queued over a small call's speculative rows (emqx_gm_publish_window):
 // device pointers into one workspace `ws` of the context's pool, which the
 // caller releases behind the stream; *total is the true hit count.
@@ -131,7 +135,7 @@ struct ShSpec {
 };
 int sh_queue_spec(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const uint64_t* d_ro, const uint32_t* d_ids, uint64_t n,
                   uint64_t cap, uint64_t cap_hits, uint32_t strategy, const uint32_t* d_hash, uint32_t seed,
-                  ShSpec* out);
+                  ShSpec* out, const uint32_t* d_win_row0 = nullptr, uint32_t n_win = 0);
 // the shadow state written into the table (queued, no wait; under sh->mu)
 int sh_queue_commit(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const ShSpec& run);
 }  // namespace gm

@@ -61,7 +61,8 @@ __global__ __launch_bounds__(256) void k_sh_expand(ShView v, const uint64_t* __r
                                                    const uint32_t* __restrict__ msg_hash, uint32_t seed,
                                                    uint32_t* __restrict__ out_slots,
                                                    uint32_t* __restrict__ out_members,
-                                                   uint32_t* st_out) {
+                                                   uint32_t* st_out, const uint32_t* __restrict__ win_row0,
+                                                   uint32_t n_win) {
   const uint64_t j = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (j >= nnz) return;
   const uint32_t f = ids[j];
@@ -79,6 +80,17 @@ __global__ __launch_bounds__(256) void k_sh_expand(ShView v, const uint64_t* __r
       else hi = mid;
     }
     row = lo;
+    // a group of windows (gm_publish.hip): random's row is the message's row in its OWN window --
+    // the last window w with win_row0[w] <= row (windows without a topic repeat a first row)
+    if (win_row0 && strategy == EMQX_GM_SHARE_RANDOM) {
+      uint32_t a = 0, b = n_win;
+      while (b - a > 1) {
+        const uint32_t mid = a + (b - a) / 2;
+        if (win_row0[mid] <= row) a = mid;
+        else b = mid;
+      }
+      row -= win_row0[a];
+    }
   }
   for (uint32_t s = s0; s < s1 && h < hits; ++s, ++h) {
     out_slots[h] = s;
@@ -231,7 +243,7 @@ int sh_read_state(emqx_gm_ctx* ctx, const emqx_gm_shared* sh, std::vector<uint32
 
 int sh_pick_device(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, uint32_t strategy,
                    const uint32_t* msg_hash, uint32_t seed, uint32_t n_chunks, emqx_gm_csr* out_members,
-                   emqx_gm_csr* out_slots, bool host_out, uint32_t* waits) {
+                   emqx_gm_csr* out_slots, bool host_out, uint32_t* waits, const uint32_t* d_win_row0, uint32_t n_win) {
   GM_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   // (host_out: device rows, but host hashes and a host result -- a publish window's rerun, gm_publish.hip)
@@ -363,7 +375,7 @@ int sh_pick_device(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, u
     return set_err(ctx, EMQX_GM_ENOMEM, "shared_pick: result ids");
   // expand (and pick, but for round robin)
   hipLaunchKernelGGL(k_sh_expand, dim3(blocks_of(nnz)), dim3(256), 0, st, sh->dv, d_mro, n, d_mids, nnz,
-                     d_hoff.as<uint64_t>(), hits, strategy, d_hash, seed, o_slot, o_mem, sh->dv.st);
+                     d_hoff.as<uint64_t>(), hits, strategy, d_hash, seed, o_slot, o_mem, sh->dv.st, d_win_row0, n_win);
   GM_HIP(ctx, hipGetLastError());
   GM_HIP(ctx, hipEventRecord(ev.e[2], st));
   if (strategy == EMQX_GM_SHARE_ROUND_ROBIN) {
@@ -412,7 +424,7 @@ int sh_pick_device(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const emqx_gm_csr* m, u
 // (no room, or a workspace past the cap).
 int sh_queue_spec(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const uint64_t* d_ro, const uint32_t* d_ids, uint64_t n,
                   uint64_t cap, uint64_t cap_hits, uint32_t strategy, const uint32_t* d_hash, uint32_t seed,
-                  ShSpec* out) {
+                  ShSpec* out, const uint32_t* d_win_row0, uint32_t n_win) {
   hipStream_t st = ctx->stream;
   const uint64_t S = sh->hv.n_slots;
   if (!S || !cap || !cap_hits) return 1;  // (a table without slots: the exact call answers without device work)
@@ -466,7 +478,7 @@ int sh_queue_spec(emqx_gm_ctx* ctx, emqx_gm_shared* sh, const uint64_t* d_ro, co
                      static_cast<uint64_t*>(nullptr));
   SH_Q(hipGetLastError());
   hipLaunchKernelGGL(k_sh_expand, dim3(blocks_of(cap)), dim3(256), 0, st, sh->dv, d_ro, n, d_ids, cap, hoff, cap_hits,
-                     strategy, d_hash, seed, out->slots, out->members, out->sh_st);
+                     strategy, d_hash, seed, out->slots, out->members, out->sh_st, d_win_row0, n_win);
   SH_Q(hipGetLastError());
   if (rr) {
     uint32_t* hist = static_cast<uint32_t*>(at(o_hist));

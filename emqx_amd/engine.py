@@ -518,6 +518,53 @@ class Context:
         finally:
             lib().emqx_gm_publish_result_free(self.h, C.byref(res))
 
+    def publish_windows(self, index: Index, windows, hashes=None, exact: bool = True, shared=None,
+                        strategy="round_robin", seed: int = 0, dests=None, skip_node: Optional[int] = None,
+                        group_stats: bool = False):
+        """Many whole publish windows in one call (emqx_gm_publish_windows):
+        ``windows`` is a sequence of topic lists (or packed pairs), ``hashes`` one
+        array per window (``strategy="hash"``).  Returns one ``(matches,
+        deliveries, picks, plan, stats)`` per window, each what ``publish_window``
+        gives when the windows are run one after another, in order; the windows
+        run grouped, one device round trip per held group.  With
+        ``group_stats`` each ``stats`` also carries the window's
+        emqx_gm_publish_group_stats under ``"group"``."""
+        from .cluster import _skip
+        from .shared import _strategy
+        packed = [t if isinstance(t, tuple) else pack(t) for t in windows]
+        n = len(packed)
+        if hashes is not None and len(hashes) != n:
+            raise ValueError("one hash array per window")
+        w = (_lib.PublishWin * max(n, 1))()
+        keep = []
+        for k, (tb, to) in enumerate(packed):
+            w[k].w.topic_bytes, w[k].w.topic_off, w[k].w.n_topics = tb.ctypes.data, to.ctypes.data, len(to) - 1
+            if hashes is not None and hashes[k] is not None:
+                hs = np.ascontiguousarray(hashes[k], np.uint32)
+                if len(hs) != len(to) - 1:
+                    raise ValueError("one hash per topic")
+                if len(hs) == 0:
+                    hs = np.zeros(1, np.uint32)
+                keep.append(hs)
+                w[k].msg_hash = hs.ctypes.data
+        o = _lib.PublishOpts()
+        o.flags = _lib.WITH_EXACT if exact else 0
+        o.shared = shared.h if shared is not None else None
+        o.strategy = _strategy(strategy)
+        o.seed = seed & 0xFFFFFFFF
+        o.dests = dests.h if dests is not None else None
+        o.skip_node = _skip(skip_node)
+        res = (_lib.PublishResult * max(n, 1))()
+        st = (_lib.PublishStats * max(n, 1))()
+        gs = (_lib.PublishGroupStats * max(n, 1))()
+        check(lib().emqx_gm_publish_windows(self.h, index.h, w, n, C.byref(o), res, st, gs), self.h, "publish_windows")
+        try:
+            return [_publish_result(res[k], st[k], gs[k] if group_stats else None, shared is not None,
+                                    dests is not None) for k in range(n)]
+        finally:
+            for k in range(n):
+                lib().emqx_gm_publish_result_free(self.h, C.byref(res[k]))
+
     def match_windows(self, index: Index, windows, exact: bool = True, fanout: bool = True):
         """Many publish windows in one call (emqx_gm_match_windows): ``windows`` is a
         sequence of topic lists (or packed ``(bytes, offsets)`` pairs).  Returns one
@@ -688,6 +735,24 @@ class Context:
         return db.value, do.value, int(tot.value)
 
 
+def _publish_result(res, st, gs, with_picks: bool, with_plan: bool):
+    """(matches, deliveries, picks, plan, stats) of one emqx_gm_publish_result, as publish_window's."""
+    from .cluster import _plan_to_numpy
+    picks = plan = None
+    if with_picks:
+        ro, mem = _csr_to_numpy(res.pick_members)
+        ro2, slots = _csr_to_numpy(res.pick_slots)
+        assert np.array_equal(ro, ro2)
+        picks = (ro, mem, slots)
+    if with_plan:
+        plan = _plan_to_numpy(res.forwards)
+    stats = {name: int(getattr(st, name)) for name, _ in _lib.PublishStats._fields_}
+    if gs is not None:
+        stats["group"] = {name: int(getattr(gs, name)) for name, _ in _lib.PublishGroupStats._fields_
+                          if name != "reserved8"}
+    return _csr_to_numpy(res.matches), _csr_to_numpy(res.deliveries), picks, plan, stats
+
+
 # ---------------------------------------------------------------------- sharding helpers (host)
 class Combiner:
     """emqx_gm_combiner: ``match_fanout`` / ``match`` are the context's calls of
@@ -722,6 +787,37 @@ class Combiner:
 
     def match(self, index: Index, topics, exact: bool = True):
         return self._call(index, topics, exact, False)
+
+    def publish_window(self, index: Index, topics, exact: bool = True, shared=None, strategy="round_robin",
+                       hashes=None, seed: int = 0, dests=None, skip_node: Optional[int] = None):
+        """``Context.publish_window`` through the queue (emqx_gm_combiner_publish):
+        the same tuple, its ``stats`` also carrying under ``"group"`` the group's
+        sequence number and the window's position in it (the order in which
+        windows with a stateful strategy took effect)."""
+        from .cluster import _skip
+        from .shared import _strategy
+        tb, to = topics if isinstance(topics, tuple) else pack(topics)
+        n = len(to) - 1
+        hs = None if hashes is None else np.ascontiguousarray(hashes, np.uint32)
+        if hs is not None and len(hs) != n:
+            raise ValueError("one hash per topic")
+        if hs is not None and len(hs) == 0:
+            hs = np.zeros(1, np.uint32)
+        o = _lib.PublishOpts()
+        o.flags = _lib.WITH_EXACT if exact else 0
+        o.shared = shared.h if shared is not None else None
+        o.strategy = _strategy(strategy)
+        o.seed = seed & 0xFFFFFFFF
+        o.msg_hash = hs.ctypes.data if hs is not None else None
+        o.dests = dests.h if dests is not None else None
+        o.skip_node = _skip(skip_node)
+        res, st, gs = _lib.PublishResult(), _lib.PublishStats(), _lib.PublishGroupStats()
+        check(lib().emqx_gm_combiner_publish(self.h, index.h, _ptr(tb), _ptr(to), n, C.byref(o), C.byref(res),
+                                             C.byref(st), C.byref(gs)), self.ctx.h, "combiner_publish")
+        try:
+            return _publish_result(res, st, gs, shared is not None, dests is not None)
+        finally:
+            lib().emqx_gm_publish_result_free(self.ctx.h, C.byref(res))
 
     def stats(self) -> dict:
         s = _lib.CombinerStats()

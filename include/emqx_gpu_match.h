@@ -851,6 +851,82 @@ int emqx_gm_publish_window(emqx_gm_ctx *ctx, const emqx_gm_index *idx, const uin
 /* frees every member of a result and zeroes it */
 int emqx_gm_publish_result_free(emqx_gm_ctx *ctx, emqx_gm_publish_result *res);
 
+/* ---- whole publish windows coalesced into one device round trip (gm_publish.hip) ----
+ * Every scheduler of a node runs emqx_broker:publish/1 -> route/2 per message
+ * at once (apps/emqx/src/emqx_broker.erl:204-215, 245-293, 296-322;
+ * emqx_shared_sub:dispatch/3, emqx_shared_sub.erl:113-130), so a node has many
+ * small windows in flight, each needing rows, deliveries, picks and forwards.
+ * emqx_gm_publish_windows runs a GROUP of them as one match, one fan-out, one
+ * pick stage and one plan stage over the group's rows, and cuts every result
+ * back into the windows' own, with ONE host-blocking wait per held group and
+ * the shared table's lock taken once per group.
+ * CONTRACT: out[k] is bit-equal to what emqx_gm_publish_window returns for
+ * window k when the windows are run one after another, in order, on the same
+ * tables with the same (flags, shared, strategy, seed, dests, skip_node) --
+ * every array, n_pairs, row_routes, and the shared table's round-robin / sticky
+ * state afterwards.  Round robin: the concatenated rows' hits take consecutive
+ * ranks per slot; sticky: every hit of a slot computes the same first member;
+ * hash: the windows' msg_hash arrays are concatenated in window order; random
+ * mixes a message's row in its OWN window (the kernel subtracts the window's
+ * first row); a node's forwards of a window are one contiguous run of the
+ * node's group list, cut at a lower bound on the row.  Each out[k] is freed on
+ * its own with emqx_gm_publish_result_free, from any thread.
+ * GROUPS as emqx_gm_match_windows: at most 64 windows, one chunk of topics and
+ * 1 MiB of text (the hashes travel beside the text and do not count); more
+ * windows run as groups one after another, state carried from group to group.
+ * A window a group cannot hold (an overlay or sharded snapshot, an index
+ * without subscriber lists, a topic past 65,535 B, more than 1 MiB of text)
+ * runs alone through emqx_gm_publish_window, in its place.  A group runs on
+ * the first listed device, which holds the side tables.  With both tables NULL
+ * the call is emqx_gm_match_windows with deliveries.
+ * FALLBACKS, each visible in the stats: a group whose rows were not the
+ * speculative ones, or whose hits (pairs) pass the GROUP's capacity, has that
+ * side result run again at its exact size on the true device rows (a second
+ * round trip) and cut on the host; a window past its OWN capacity while the
+ * group held gets a result of exact size and its cut again, the others pay
+ * nothing; deliveries follow emqx_gm_match_windows' rule.  The plan is settled
+ * before the picks and the commit of the shared state comes last.
+ * ERRORS: a NULL argument, unknown flags, non-monotone offsets in any window, a
+ * strategy out of range, EMQX_GM_SHARE_HASH with a window lacking msg_hash,
+ * opts->msg_hash non-NULL, a table bound elsewhere: EMQX_GM_EINVAL /
+ * EMQX_GM_EUNSUPPORTED before any device work, no output touched, no state
+ * changed.  On a later error every output is zeroed and nothing is held.
+ *
+ * emqx_gm_combiner_publish: emqx_gm_publish_window through a combiner.  Publish
+ * windows group only with publish windows of the same (index, flags, shared,
+ * strategy, seed, dests, skip_node); a caller's bad window fails that call
+ * alone.  Stateful strategies make the order of the groups observable, so it is
+ * reported: `where` carries the combiner's group sequence number and the
+ * window's position in its group, and groups with a stateful strategy are
+ * serialised in sequence order.  Replaying all windows through
+ * emqx_gm_publish_window in (seq, position) order gives the same results and
+ * the same final state. */
+typedef struct {
+  emqx_gm_window w;
+  const uint32_t *msg_hash; /* host, w.n_topics entries; required for EMQX_GM_SHARE_HASH */
+} emqx_gm_publish_win;
+typedef struct {
+  uint64_t seq;           /* the group's sequence number: per combiner, or per call (from 0)     */
+  uint32_t position;      /* the window's place in its group                                     */
+  uint32_t n_windows;     /* windows of the group (1: also a window that ran alone)              */
+  uint32_t device_waits;  /* host-blocking waits the whole group made (0: alone, not counted)    */
+  uint8_t grouped;        /* 1: run by the group stage; 0: alone through emqx_gm_publish_window  */
+  uint8_t rows_spec, picks_spec, forwards_spec; /* 1: the GROUP's part came from the first round trip */
+  uint8_t window_picks_exact, window_forwards_exact; /* 1: the group held, this window passed its own capacity */
+  uint8_t reserved8[6];
+  uint64_t cap_hits, cap_pairs; /* the group's speculative capacities (0: not speculated)        */
+  uint64_t n_hits, n_pairs;     /* the group's hits and pairs                                    */
+} emqx_gm_publish_group_stats;
+int emqx_gm_publish_windows(emqx_gm_ctx *ctx, const emqx_gm_index *idx, const emqx_gm_publish_win *windows,
+                            uint32_t n_windows, const emqx_gm_publish_opts *opts /* msg_hash must be NULL */,
+                            emqx_gm_publish_result *out /* [n_windows] */,
+                            emqx_gm_publish_stats *stats /* [n_windows] or NULL */,
+                            emqx_gm_publish_group_stats *gstats /* [n_windows] or NULL */);
+int emqx_gm_combiner_publish(emqx_gm_combiner *cb, const emqx_gm_index *idx, const uint8_t *topic_bytes,
+                             const uint64_t *topic_off, uint64_t n_topics, const emqx_gm_publish_opts *opts,
+                             emqx_gm_publish_result *out, emqx_gm_publish_stats *stats /* may be NULL */,
+                             emqx_gm_publish_group_stats *where /* may be NULL */);
+
 /* ---- authorization check (gm_authz.cpp / gm_authz.hip): the first matching ACL rule per request ----
  * Every PUBLISH and SUBSCRIBE passes emqx_authz:authorize/5 before the router;
  * the reference scans its rule lists per packet (emqx_authz:do_authorize/4,
