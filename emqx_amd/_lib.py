@@ -23,6 +23,9 @@ SHARE_HASH, SHARE_ROUND_ROBIN, SHARE_STICKY, SHARE_RANDOM = 0, 1, 2, 3
 DESTS_MAX_NODES = 4096
 DESTS_NO_SKIP = 0xFFFFFFFF
 DESTS_SKIP_UNKNOWN = 0x1
+SO_SKIP_UNKNOWN = 0x1
+SO_NO_PUBLISHER = 0xFFFFFFFF
+SO_FLAG, SO_DROP = 0, 1
 OPEN_MIRROR_EAGER = 0x1
 OPEN_MIRROR_LAZY = 0x2
 IMAGE_NO_BLOB = 0x1
@@ -104,6 +107,16 @@ class Forwards(C.Structure):
                 ("rows", C.POINTER(C.c_uint32)), ("filters", C.POINTER(C.c_uint32)),
                 ("row_routes", C.POINTER(C.c_uint32)), ("n_nodes", C.c_uint32), ("on_device", C.c_int32),
                 ("priv", C.c_void_p)]
+
+
+class SubOptsInfo(C.Structure):
+    _fields_ = [("n_entries", C.c_uint64), ("n_defaulted", C.c_uint64), ("n_nl", C.c_uint64),
+                ("n_skipped_unknown", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
+class Deliveries(C.Structure):
+    _fields_ = [("deliveries", Csr), ("dopt", C.POINTER(C.c_uint8)), ("row_dropped", C.POINTER(C.c_uint32)),
+                ("n_dropped", C.c_uint64)]
 
 
 class PublishOpts(C.Structure):
@@ -228,6 +241,12 @@ SIGNATURES = {
     "emqx_gm_forwards_free": (_i32, [_vp, C.POINTER(Forwards)]),
     "emqx_gm_dests_info": (_i32, [_vp, C.POINTER(DestsInfo)]),
     "emqx_gm_dests_release": (_i32, [_vp]),
+    "emqx_gm_subopts_build": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, C.c_uint8, _u32, C.POINTER(_vp)]),
+    "emqx_gm_deliver": (_i32, [_vp, _vp, C.POINTER(Csr), _vp, _vp, _u32, C.POINTER(Deliveries)]),
+    "emqx_gm_subopts_index": (_vp, [_vp]),
+    "emqx_gm_deliveries_free": (_i32, [_vp, C.POINTER(Deliveries)]),
+    "emqx_gm_subopts_info": (_i32, [_vp, C.POINTER(SubOptsInfo)]),
+    "emqx_gm_subopts_release": (_i32, [_vp]),
     "emqx_gm_publish_window": (_i32, [_vp, _vp, _vp, _vp, _u64, C.POINTER(PublishOpts), C.POINTER(PublishResult),
                                       C.POINTER(PublishStats)]),
     "emqx_gm_publish_result_free": (_i32, [_vp, C.POINTER(PublishResult)]),
@@ -272,6 +291,11 @@ SIGNATURES = {
     "emqx_gm_forwards_free_host": (_i32, [C.POINTER(Forwards)]),
     "emqx_gm_forward_plan_chunked": (_i32, [_vp, _vp, C.POINTER(Csr), _u32, _u32, C.POINTER(Forwards)]),
     "emqx_gm_dests_last_times": (_i32, [_vp, C.POINTER(C.c_double)]),
+    "emqx_gm_subopts_compile_host": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.c_uint8, _u32,
+                                            C.POINTER(_vp)]),
+    "emqx_gm_deliver_host": (_i32, [_vp, C.POINTER(Csr), _vp, _vp, _u32, C.POINTER(Deliveries)]),
+    "emqx_gm_deliveries_free_host": (_i32, [C.POINTER(Deliveries)]),
+    "emqx_gm_subopts_last_times": (_i32, [_vp, C.POINTER(C.c_double)]),
     "emqx_gm_authz_compile_host": (_i32, [C.POINTER(AuthzDesc), C.POINTER(_vp)]),
     "emqx_gm_authz_check_host": (_i32, [_vp, C.POINTER(AuthzBatch), _vp, _vp]),
     "emqx_gm_authz_last_kernel_ms": (_i32, [_vp, C.POINTER(C.c_double)]),

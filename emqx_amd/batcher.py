@@ -63,6 +63,29 @@ def is_sys(topic: bytes) -> bool:
     return topic.startswith(b"$SYS/")
 
 
+class _IdsOpts:
+    """A filter's segment of a window's deliveries with the option bytes beside
+    the ids (``GpuRoutes.groups_opts``); ``dropped``: its No-Local removals."""
+    __slots__ = ("ids", "dopt", "dropped")
+
+    def __init__(self, ids, dopt, dropped=0):
+        self.ids, self.dopt, self.dropped = ids, dopt, dropped
+
+    def __len__(self):
+        return len(self.ids)
+
+    def tolist(self):
+        return self.ids.tolist()
+
+
+def msg_meta(topic, msg):
+    """The default ``PublishBatcher(msg_meta=)``: (qos, retain, from[, headers.retained])
+    of a message given as a dict with those keys; anything else is (0, False, None)."""
+    if isinstance(msg, dict):
+        return (msg.get("qos", 0), bool(msg.get("retain")), msg.get("from"), bool(msg.get("retained")))
+    return (0, False, None, False)
+
+
 class GpuRoutes:
     """The aggregator's index over the route filters, with the local
     subscribers' ids as fan-out lists (mirror of the gen_server state of
@@ -86,9 +109,17 @@ class GpuRoutes:
         self.stale = False
         self._names: Dict[int, bytes] = {}     # filter id -> bytes of the current snapshot
         self._lock = threading.Lock()
+        self.opts: Dict[Tuple[bytes, int], int] = {}  # (filter, subscriber id) -> option byte, where given
+        self.subopts_on = False                # a subscription gave options, or a batcher asked for them
+        self._so_table = None                  # the SubOptTable of the current snapshot
+        self._so_index_h = None
+        self._so_dirty = True
+        self.subopts_builds = 0
 
     # ---- maintenance (handle_call subscribe / unsubscribe / route, 'DOWN')
-    def subscribe(self, filt, sub) -> None:
+    def subscribe(self, filt, sub, opts=None) -> None:
+        """``opts``: the subscription's options (a ``pack_opt`` byte or its keyword
+        dict: qos, nl, rap, upgrade_qos); None leaves the pair at the default."""
         f = _b(filt)
         with self._lock:
             sid = self.ids.get(sub)
@@ -96,6 +127,10 @@ class GpuRoutes:
                 sid = self.ids[sub] = self._next_id
                 self._next_id += 1
                 self.subs[sid] = sub
+            if opts is not None:
+                from .subopts import pack_opt
+                self.opts[(f, sid)] = pack_opt(**opts) if isinstance(opts, dict) else int(opts)
+                self.subopts_on = self._so_dirty = True
             self.filters_of.setdefault(sub, set()).add(f)
             self.ops.append((f, sid, "subscribe"))
 
@@ -106,6 +141,8 @@ class GpuRoutes:
             if sid is None:
                 return
             self.filters_of.get(sub, set()).discard(f)
+            if self.opts.pop((f, sid), None) is not None:
+                self._so_dirty = True
             self.ops.append((f, sid, "unsubscribe"))
 
     def subscriber_down(self, sub) -> None:
@@ -115,6 +152,8 @@ class GpuRoutes:
             if sid is None:
                 return
             for f in sorted(self.filters_of.pop(sub, set())):
+                if self.opts.pop((f, sid), None) is not None:
+                    self._so_dirty = True
                 self.ops.append((f, sid, "unsubscribe"))
             self.subs.pop(sid, None)
 
@@ -149,6 +188,7 @@ class GpuRoutes:
             ops, self.ops = self.ops, []
         if not ops:
             self.stale = False
+            self._refresh_subopts()
             return
         try:
             new = self.ctx.update_subs(self.index, ops)
@@ -160,6 +200,25 @@ class GpuRoutes:
         self.index, self._names = new, {}
         self.updates += 1
         self.stale = False
+        self._refresh_subopts()
+
+    def _refresh_subopts(self) -> None:
+        """The option table of the current snapshot, beside the destination table:
+        rebuilt when an option changed or the snapshot is another one (the table
+        is immutable; an entry whose pair the snapshot does not hold -- its
+        subscribe is still queued -- is left out of this build)."""
+        if not self.subopts_on or self.stale:
+            return
+        if self._so_table is not None and not self._so_dirty and self._so_index_h is self.index.h:
+            return
+        with self._lock:
+            entries = [(f, sid, o) for (f, sid), o in self.opts.items()]
+            self._so_dirty = False
+        new = self.ctx.build_subopts(self.index, entries, default=0, skip_unknown=True)
+        if self._so_table is not None:
+            self._so_table.release()
+        self._so_table, self._so_index_h = new, self.index.h
+        self.subopts_builds += 1
 
     # ---- the batch call (fanout_batch/2)
     def groups(self, topics: Sequence[bytes]) -> List[Row]:
@@ -176,6 +235,41 @@ class GpuRoutes:
         # (with a combiner: the same call, coalesced with the windows of concurrent callers)
         (ro, ids), (fro, fids) = (self.combiner or self.ctx).match_fanout(idx, list(topics), exact=True)
         return self._cut(idx, ro, ids, fro, fids), idx, (ro, ids)
+
+    def groups_opts(self, topics: Sequence[bytes], msg_flags, msg_from, drop: bool = False) -> List[Row]:
+        """``groups`` with the option bytes: each (filter, _IdsOpts) carries the
+        segment's ids and their delivery bytes (emqx_gm_deliver, FLAG mode, on
+        the window's matched rows); with ``drop`` the marked deliveries are
+        removed here and counted in the segment's ``dropped``."""
+        self.subopts_on = True
+        self.refresh()
+        if self.stale:
+            raise RuntimeError("stale_index")
+        idx, tab = self.index, self._so_table
+        ro, ids = self.ctx.match(idx, list(topics), exact=True)
+        # FLAG mode: the deliveries are the fan-out's, so a row is cut per filter by the snapshot's own
+        # counts; the device's bit 4 is the one verdict on No Local, and `drop` removes what it marks
+        d = tab.deliver((ro, ids), msg_flags, msg_from, False, index=idx)
+        out = []
+        for k in range(len(ro) - 1):
+            row, pos = [], int(d.row_off[k])
+            for f in ids[ro[k]:ro[k + 1]].tolist():
+                c = idx.subscriber_count(f)
+                name = self._names.get(f)
+                if name is None:
+                    name = self._names[f] = idx.filter(f)
+                sids, bytes_, gone = d.ids[pos:pos + c], d.dopt[pos:pos + c], 0
+                if drop:
+                    keep = (bytes_ & 0x10) == 0
+                    gone = int(c - keep.sum())
+                    if gone:
+                        sids, bytes_ = sids[keep], bytes_[keep]
+                row.append((name, _IdsOpts(sids, bytes_, gone)))
+                pos += c
+            if pos != int(d.row_off[k + 1]):
+                raise RuntimeError("deliveries do not add up to the snapshot's subscriber counts")
+            out.append(row)
+        return out
 
     def _cut(self, idx, ro, ids, fro, fids) -> List[Row]:
         """Each fan-out row cut back into one segment per matched filter."""
@@ -262,7 +356,20 @@ class PublishBatcher:
     calls above; the results are the same.  With ``routes`` built over a
     combiner (``GpuRoutes(ctx, combiner=cb)``) that call goes through it
     (emqx_gm_combiner_publish): whole windows of concurrent batchers share one
-    device round trip."""
+    device round trip.
+
+    ``subopts`` (needs ``routes``; not with ``shared`` / ``cluster`` yet): the
+    window's local deliveries come from ``routes.groups_opts`` (one match, one
+    emqx_gm_deliver) with the byte emqx_session:enrich_deliver/2 would compute
+    beside every subscriber id, and ``deliver`` is called as ``deliver(sub,
+    filter, msg, byte)`` (``unpack_dopt``).  ``msg_meta(topic, msg) -> (qos,
+    retain, from[, headers.retained])`` reads a message; ``from`` is the
+    publishing subscriber as ``routes.ids`` knows it, or None.
+    ``drop_no_local`` removes the deliveries the device marked as No-Local hits
+    (bit 4) and counts them in ``metrics['delivery.dropped.no_local']``;
+    otherwise the bit goes to ``deliver`` and the session drops what
+    ignore_local/4 would.  Without
+    ``subopts`` nothing changes."""
 
     def __init__(self, groups_fn: Optional[Callable[[Sequence[bytes]], List[Row]]] = None, max_batch: int = 4096,
                  window_s: float = 0.001, subscribers: Optional[Dict[int, object]] = None,
@@ -278,7 +385,8 @@ class PublishBatcher:
                  routes: Optional[GpuRoutes] = None, shared=None, shared_strategy: str = "round_robin",
                  shared_hash: Optional[Callable[[bytes, object], int]] = None, cluster=None,
                  forward_batch: Optional[Callable[[bytes, List[Tuple[bytes, object]]], object]] = None,
-                 one_call: bool = False):
+                 one_call: bool = False, subopts: bool = False, drop_no_local: bool = False,
+                 msg_meta: Callable[[bytes, object], tuple] = msg_meta):
         if routes is None and isinstance(getattr(groups_fn, "__self__", None), GpuRoutes):
             routes = groups_fn.__self__
         if groups_fn is None:
@@ -296,6 +404,9 @@ class PublishBatcher:
             raise TypeError("PublishBatcher(cluster=...) needs routes (the window's matched rows)")
         if one_call and routes is None:
             raise TypeError("PublishBatcher(one_call=True) needs routes (the window call)")
+        if subopts and (routes is None or shared is not None or cluster is not None):
+            raise TypeError("PublishBatcher(subopts=True) needs routes, without shared / cluster")
+        self.subopts, self.drop_no_local, self.msg_meta = subopts, drop_no_local, msg_meta
         self.one_call = one_call
         self.routes, self.shared, self.shared_strategy = routes, shared, shared_strategy
         self.cluster = cluster
@@ -317,6 +428,8 @@ class PublishBatcher:
         self.on_dropped = on_dropped or (lambda msg: None)
         self.persist = persist or (lambda topic, msg: None)
         self.metrics = {"messages.publish": 0, "messages.dropped": 0, "messages.dropped.no_subscribers": 0}
+        if subopts:
+            self.metrics["delivery.dropped.no_local"] = 0
         self.batches = 0
         self.messages = 0
         self._mlock = threading.Lock()
@@ -410,6 +523,13 @@ class PublishBatcher:
                 if self.cluster is None:
                     return [("ok", r, p) for r, p in zip(rows, picks)]
                 return [("ok", r, p, w) for r, p, w in zip(rows, picks, self._forward_window(idx, csr, msgs, plan))]
+            if self.subopts:  # the window's deliveries with their option bytes: one match, one deliver call
+                from .subopts import pack_msg
+                msgs = msgs if msgs is not None else [None] * len(topics)
+                meta = [tuple(self.msg_meta(t, m)) + (False,) for t, m in zip(topics, msgs)]
+                flags = [pack_msg(q, rt, hdr) for q, rt, _, hdr, *_ in meta]
+                froms = [self.routes.ids.get(frm) if frm is not None else None for _, _, frm, *_ in meta]
+                return [("ok", r) for r in self.routes.groups_opts(list(topics), flags, froms, self.drop_no_local)]
             return [("ok", r) for r in self.groups_fn(list(topics))]
         except Exception as e:  # the NIF's {error, _}: every caller takes the reference path
             return [("error", str(e))] * len(topics)
@@ -481,7 +601,7 @@ class PublishBatcher:
     def route_row(self, row, topic: bytes, msg) -> Result:
         """route(aggre(Routes)) over a matched row (emqx_broker.erl:245-273)."""
         if row[0] == "ok":
-            routes: List[tuple] = [(f, self.node, ids) for f, ids in row[1] if len(ids)]
+            routes: List[tuple] = [(f, self.node, ids) for f, ids in row[1] if len(ids) or getattr(ids, "dropped", 0)]
             sent = row[3] if len(row) > 3 else None  # the window's forwards of this row: [(node, filter, result)]
             other = [(f, d) for f, _ in row[1] if f in self.others for d in self.lookup_routes(f)
                      if isinstance(d, tuple) or (sent is None and _b(d) != self.node)]
@@ -534,6 +654,18 @@ class PublishBatcher:
     def dispatch_ids(self, f: bytes, ids, topic: bytes, msg):
         """do_dispatch/2,3: one delivery per live subscriber; none live is a drop."""
         n = 0
+        if isinstance(ids, _IdsOpts):  # the option byte goes with the id: deliver(sub, filter, msg, byte)
+            for sid, b in zip(ids.ids.tolist(), ids.dopt.tolist()):
+                sub = self.subscribers.get(int(sid))
+                if sub is not None and self.deliver(sub, f, msg, b):
+                    n += 1
+            if ids.dropped:  # delivered to its session and dropped there as no_local: not a no_subscribers drop
+                with self._mlock:
+                    self.metrics["delivery.dropped.no_local"] += ids.dropped
+            if n or ids.dropped:
+                return ("ok", n)
+            self.dropped(topic, msg)
+            return ("error", "no_subscribers")
         for sid in (ids.tolist() if hasattr(ids, "tolist") else ids):
             sub = self.subscribers.get(int(sid))
             if sub is not None and self.deliver(sub, f, msg):

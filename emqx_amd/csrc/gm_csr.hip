@@ -487,6 +487,14 @@ int queue_fanout_spec(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint64_t
   return 0;
 }
 
+// k_fanout_rowoff for another file's segment offsets (gm_subopts.hip: a deliver
+// call cuts its rows the way the fan-out does)
+int launch_fanout_rowoff(hipStream_t st, const uint64_t* m_off, uint64_t n, const uint64_t* seg_dst, uint64_t* out_off,
+                         uint64_t nseg) {
+  hipLaunchKernelGGL(k_fanout_rowoff, dim3((n + 1 + 255) / 256), dim3(256), 0, st, m_off, n, seg_dst, out_off, nseg);
+  return hipGetLastError() == hipSuccess ? 0 : EMQX_GM_EDEVICE;
+}
+
 // Rows back in their batch order after a prefix-routed exchange (sharded.py,
 // gm_route.hip): out row perm[i] = input row i, the input rows packed in send
 // order with u32 lengths lens[i].

@@ -437,6 +437,9 @@ int launch_off64_to_32(hipStream_t st, const uint64_t* in, uint64_t n1, uint32_t
 int launch_copy_u32x2(hipStream_t st, const uint32_t* s0, uint32_t* d0, uint64_t n0, const uint32_t* s1, uint32_t* d1,
                       uint64_t n1, const uint64_t* n1_max = nullptr);
 int launch_add_u64(hipStream_t st, uint64_t* p, uint64_t n1, uint64_t add);
+// the fan-out's row offsets from segment offsets: out_off[i] = seg_dst[min(m_off[i], nseg)], i in [0, n]
+int launch_fanout_rowoff(hipStream_t st, const uint64_t* m_off, uint64_t n, const uint64_t* seg_dst, uint64_t* out_off,
+                         uint64_t nseg);
 // prefix sharding (gm_route.hip) and the exchange's device steps
 int route_plan(const uint8_t* fb, const uint64_t* fo, uint64_t n, uint32_t n_shards, uint32_t* shard_out,
                emqx_gm_route** out);

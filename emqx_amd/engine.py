@@ -388,6 +388,18 @@ class Context:
         from .cluster import build_dests
         return build_dests(self, index, routes, n_nodes, skip_unknown)
 
+    def build_subopts(self, index: Index, entries, default: int = 0, skip_unknown: bool = False):
+        """A subscription-option table bound to ``index`` (emqx_gm_subopts_build):
+        ``entries`` is [(filter, subscriber id, opt)], see :mod:`emqx_amd.subopts`."""
+        from .subopts import build_subopts
+        return build_subopts(self, index, entries, default, skip_unknown)
+
+    def deliver(self, index: Index, table, rows, msg_flags, msg_from=None, drop: bool = False):
+        """The deliveries of ``rows`` (a match on ``index``, the snapshot ``table``
+        is bound to) with one option byte each (emqx_gm_deliver): host rows, see
+        ``SubOptTable.deliver``."""
+        return table.deliver(rows, msg_flags, msg_from, drop, index=index)
+
     def build_authz(self, table):
         """An authorization table (emqx_gm_authz_build) from an ``AuthzTable``:
         the chain of file and built-in-database sources compiled into HBM, see

@@ -228,6 +228,7 @@ class Broker:
     delivery multiset is the same (the reference promises no order either)."""
 
     SHARD = 1024  # emqx_broker_helper.erl:54
+    DEFAULT_SUBOPTS = {"rh": 0, "rap": 0, "nl": 0, "qos": 0}  # include/emqx_mqtt.hrl:193-197
 
     def __init__(self, ctx: Optional[Context] = None, schedulers: int = 8):
         self.ctx = ctx
@@ -237,6 +238,7 @@ class Broker:
         self._shards: Dict[Tuple[bytes, int], List[int]] = {}
         self._seq: Dict[bytes, int] = {}
         self._subopt: set = set()
+        self._subopts: Dict[Tuple[int, bytes], dict] = {}  # the ?SUBOPTION table: {SubPid, Topic} -> SubOpts
         self._snap: Optional[_Snapshot] = None
         self._pending: List[Tuple[bytes, int, bool]] = []  # since the snapshot: (filter, subscriber, subscribe)
         self._lock = threading.Lock()
@@ -246,12 +248,18 @@ class Broker:
             self.ctx = self.router._context()
         return self.ctx
 
-    def subscribe(self, t, subpid: int) -> None:
+    def subscribe(self, t, subpid: int, subopts: Optional[dict] = None) -> None:
+        """subscribe/3: ``subopts`` merged over ?DEFAULT_SUBOPTS (emqx_broker.erl:128);
+        an existing subscription given options again has them replaced
+        (set_subopts, emqx_broker.erl:135-137)."""
         t = _b(t)
         with self._lock:
             if (subpid, t) in self._subopt:
+                if subopts is not None:
+                    self._subopts[(subpid, t)] = {**self.DEFAULT_SUBOPTS, **subopts}
                 return
             self._subopt.add((subpid, t))
+            self._subopts[(subpid, t)] = {**self.DEFAULT_SUBOPTS, **(subopts or {})}
             s = self._seq[t] = self._seq.get(t, 0) + 1
             if s <= self.SHARD:
                 self._direct.setdefault(t, []).append(subpid)
@@ -268,6 +276,7 @@ class Broker:
             if (subpid, t) not in self._subopt:
                 return
             self._subopt.discard((subpid, t))
+            self._subopts.pop((subpid, t), None)
             if subpid in self._direct.get(t, []):
                 self._direct[t].remove(subpid)
             for k in [k for k in self._shards if k[0] == t]:
@@ -277,6 +286,12 @@ class Broker:
             still = bool(self._direct.get(t)) or any(v for k, v in self._shards.items() if k[0] == t)
         if not still:
             self.router.delete_route(t)
+
+    def get_subopts(self, t, subpid: int) -> Optional[dict]:
+        """get_subopts/2 (emqx_broker.erl:375-377): the subscription's options, None without one."""
+        with self._lock:
+            o = self._subopts.get((subpid, _b(t)))
+            return dict(o) if o is not None else None
 
     def subscribers(self, t) -> List[int]:
         """subscribers/1 with the shard markers expanded (do_dispatch/3)."""

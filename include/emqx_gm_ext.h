@@ -185,6 +185,29 @@ int emqx_gm_forward_plan_chunked(emqx_gm_ctx *ctx, emqx_gm_dests *dt, const emqx
                                  uint32_t skip_node, uint32_t n_chunks, emqx_gm_forwards *out);
 int emqx_gm_dests_last_times(const emqx_gm_dests *dt, double *ms4);
 
+/* Test and measurement support for the subscription-option table (no product
+ * path uses these).  compile_host: the table compiled on the host alone against
+ * the filter set index_filter_* with the subscriber lists sub_off / sub_ids as
+ * emqx_gm_index_compile_host takes them (ids = ranks among the distinct
+ * filters, the lists of a filter given twice concatenated in input order; no
+ * device, no context); emqx_gm_deliver refuses the result.  deliver_host: the
+ * plain single-threaded walk of emqx_gm_deliver over the table's host copy
+ * (host rows; any table): the walk a caller would otherwise run per delivery,
+ * and the A/B baseline.  Its arrays are malloc'd (free with
+ * emqx_gm_deliveries_free, or, in a build without the device half,
+ * emqx_gm_deliveries_free_host).  last_times: device ms of the last
+ * emqx_gm_deliver's lengths + scan, its copy kernel, and the whole call on the
+ * stream. */
+int emqx_gm_subopts_compile_host(const uint8_t *index_filter_bytes, const uint64_t *index_filter_off,
+                                 uint64_t n_index_filters, const uint64_t *sub_off, const uint32_t *sub_ids,
+                                 const uint8_t *filter_bytes, const uint64_t *filter_off, const uint32_t *entry_subs,
+                                 const uint8_t *opts, uint64_t n_entries, uint8_t default_opt, uint32_t flags,
+                                 emqx_gm_subopts **out);
+int emqx_gm_deliver_host(const emqx_gm_subopts *so, const emqx_gm_csr *matches, const uint8_t *msg_flags,
+                         const uint32_t *msg_from, uint32_t mode, emqx_gm_deliveries *out);
+int emqx_gm_deliveries_free_host(emqx_gm_deliveries *d);
+int emqx_gm_subopts_last_times(const emqx_gm_subopts *so, double *ms3);
+
 /* Test and measurement support for the authorization table (no product path
  * uses these).  compile_host: the table compiled on the host alone (no device,
  * no context); emqx_gm_authz_check refuses it.  check_host: the walk of

@@ -784,6 +784,106 @@ int emqx_gm_dests_info(const emqx_gm_dests *dt, emqx_gm_dests_info_t *info);
 /* drops the table and its reference on the snapshot */
 int emqx_gm_dests_release(emqx_gm_dests *dt);
 
+/* ---- subscription options at dispatch (gm_subopts.cpp / gm_subopts.hip): one option byte per delivery ----
+ * A delivery {deliver, Filter, Msg} is not yet what the subscriber gets: the
+ * reference passes it through the subscription's options, keyed by (Filter,
+ * Subscriber) -- emqx_session:ignore_local/4 (apps/emqx/src/emqx_session.erl:
+ * 279-291, from emqx_channel:handle_deliver/2, emqx_channel.erl:806-842) drops a
+ * delivery whose subscription has nl = 1 when the subscriber is the publisher,
+ * and enrich_deliver/2 -> get_subopts/2 -> enrich_subopts/3 (emqx_session.erl:
+ * 560-602) sets the nl flag, the effective QoS and the retain flag.  Here the
+ * options of emqx_broker:subscribe/3 (emqx_broker.erl:126-145) live in HBM,
+ * one byte beside every subscriber id of the snapshot, and emqx_gm_deliver
+ * turns a window's matched rows into deliveries with one option byte each.
+ * TABLE: bound to ONE plain snapshot built with subscriber lists, which the
+ * table retains.  Immutable, as emqx_gm_dests is: a new snapshot or a changed
+ * option means a new build; following emqx_gm_index_update_subs incrementally
+ * is out of scope.
+ * OPT BYTE (input): bits 0-1 the subscription QoS (3: EMQX_GM_EINVAL), bit 2 nl,
+ * bit 3 rap, bit 4 the subscriber session's upgrade_qos, bits 5-7 zero (else
+ * EMQX_GM_EINVAL).  rh is not carried (it belongs to the subscribe-time retained
+ * dispatch), nor is subid (the Subscription-Identifier stays with the session).
+ * A pair of the snapshot without an entry gets the build's default_opt
+ * (?DEFAULT_SUBOPTS, include/emqx_mqtt.hrl:193-197, is 0).
+ * MESSAGE FLAGS (msg_flags[r], per row): bits 0-1 the publish QoS (3:
+ * EMQX_GM_EINVAL), bit 2 the retain flag, bit 3 headers.retained =:= true, bits
+ * 4-7 zero (else EMQX_GM_EINVAL).  msg_from[r]: the publisher's subscriber id,
+ * or EMQX_GM_SO_NO_PUBLISHER.
+ * DELIVERY BYTE (dopt[k], beside deliveries.ids[k]): bits 0-1 the effective QoS
+ * (min(SubQoS, PubQoS), max under upgrade_qos), bit 2 the retain flag (cleared
+ * unless rap = 1 or headers.retained), bit 3 the nl message flag ({nl, 1}), bit 4
+ * the No-Local hit (EMQX_GM_SO_FLAG only).
+ * NO LOCAL: the reference applies lists:dropwhile over whatever batch a channel
+ * drained from its mailbox (emqx_session.erl:281): it drops only the LEADING
+ * run of hits.  Batch boundaries are mailbox timing no window can know, so the
+ * library evaluates the predicate per delivery.  EMQX_GM_SO_FLAG removes
+ * nothing and marks (bit 4) every delivery for which ignore_local's fun returns
+ * true: a session has all it needs to reproduce dropwhile bit for bit.
+ * EMQX_GM_SO_DROP removes those deliveries (the order otherwise kept) and counts
+ * them per row (row_dropped: the delivery.dropped.no_local metric): MQTT 5
+ * section 3.8.3.1 applied to every delivery, equal to the reference whenever a
+ * subscriber's hits lead its batch.
+ * EQUIVALENCE: for row r with message M, over each matched filter F in the row's
+ * order and each subscriber S of F in list order: the delivery's hit is
+ * opts(F, S).nl == 1 andalso S =:= from(M); its byte is enrich_subopts([{nl, _},
+ * {qos, _}, {rap, _}], M, #session{upgrade_qos}) clause by clause. */
+typedef struct emqx_gm_subopts emqx_gm_subopts;
+#define EMQX_GM_SO_SKIP_UNKNOWN 0x1u       /* build flag: drop (and count) entries whose pair is not in the snapshot */
+#define EMQX_GM_SO_NO_PUBLISHER 0xFFFFFFFFu
+#define EMQX_GM_SO_FLAG 0u /* emqx_gm_deliver mode: mark No-Local hits (bit 4), remove nothing */
+#define EMQX_GM_SO_DROP 1u /* ... remove them, count them per row                             */
+typedef struct {
+  uint64_t n_entries;         /* input entries stored (distinct pairs)                        */
+  uint64_t n_defaulted;       /* pairs of the snapshot without an entry (default_opt)         */
+  uint64_t n_nl;              /* pairs with nl = 1                                            */
+  uint64_t n_skipped_unknown; /* input entries dropped under EMQX_GM_SO_SKIP_UNKNOWN          */
+  uint64_t device_bytes;      /* resident table bytes in HBM (0: host-only table)             */
+} emqx_gm_subopts_info_t;
+typedef struct {
+  emqx_gm_csr deliveries; /* row r's subscriber ids, as emqx_gm_fanout (minus the dropped)    */
+  uint8_t *dopt;          /* [deliveries.nnz] the delivery bytes                              */
+  uint32_t *row_dropped;  /* [n_rows] EMQX_GM_SO_DROP: the row's removed deliveries; else NULL */
+  uint64_t n_dropped;     /* their sum                                                        */
+} emqx_gm_deliveries;
+/* Entry i is (filter filter_bytes[filter_off[i] .. filter_off[i+1]), sub_ids[i],
+ * opts[i]).  An entry whose filter is not in the snapshot, or whose subscriber
+ * is not in that filter's list: EMQX_GM_EINVAL naming it, or, with
+ * EMQX_GM_SO_SKIP_UNKNOWN, dropped and counted.  A pair given twice with
+ * different bytes, a bad opt byte (default_opt too), an unknown flag, bad
+ * offsets: EMQX_GM_EINVAL.  A filter whose list holds one subscriber twice
+ * (built from duplicate input filters) while that pair has nl = 1:
+ * EMQX_GM_EUNSUPPORTED (the reference's bag holds a pair once; the hot path
+ * relies on at most one hit per filter).  Sharded, shard and overlay snapshots,
+ * and an index without subscriber lists: EMQX_GM_EUNSUPPORTED.  The build reads
+ * the lists back once and is O(entries + n_subs) (expected; plus a sort of each
+ * filter's nl pairs): no list is scanned per entry.  On a multi-device context
+ * the table lives on the first listed device. */
+int emqx_gm_subopts_build(emqx_gm_ctx *ctx, emqx_gm_index *idx, const uint8_t *filter_bytes,
+                          const uint64_t *filter_off, const uint32_t *sub_ids, const uint8_t *opts,
+                          uint64_t n_entries, uint8_t default_opt, uint32_t flags, emqx_gm_subopts **out);
+/* The deliveries of `matches`, rows of the bound snapshot: a host CSR, or a
+ * device CSR (on_device); msg_flags / msg_from (n_rows entries each) live on the
+ * side the rows live on and the result comes back on that side (free it with
+ * emqx_gm_deliveries_free).  A NULL argument, an unknown mode, n_rows >= 2^32 - 1,
+ * and for host inputs a non-monotone row_off, an id >= n_filters or a bad
+ * msg_flags byte: EMQX_GM_EINVAL before any device work, no output touched.  For
+ * device rows the kernels skip an id >= n_filters, clamp an offset past nnz and
+ * mask msg_flags to its low 4 bits.  The rows must be rows of the table's bound
+ * snapshot (emqx_gm_subopts_index names it): a CSR does not record its snapshot,
+ * so the callers that know it -- the Python binding and the NIF -- compare the
+ * two and refuse another snapshot's rows with EMQX_GM_EINVAL before this call.
+ * In EMQX_GM_SO_FLAG mode `deliveries` is bit-equal to emqx_gm_fanout of the
+ * same rows. */
+int emqx_gm_deliver(emqx_gm_ctx *ctx, emqx_gm_subopts *so, const emqx_gm_csr *matches, const uint8_t *msg_flags,
+                    const uint32_t *msg_from, uint32_t mode, emqx_gm_deliveries *out);
+/* the bound snapshot (NULL: a host-only table); not retained for the caller */
+const emqx_gm_index *emqx_gm_subopts_index(const emqx_gm_subopts *so);
+/* frees a result (ctx may be NULL for a result of emqx_gm_deliver_host) */
+int emqx_gm_deliveries_free(emqx_gm_ctx *ctx, emqx_gm_deliveries *d);
+int emqx_gm_subopts_info(const emqx_gm_subopts *so, emqx_gm_subopts_info_t *info);
+/* drops the table and its reference on the snapshot */
+int emqx_gm_subopts_release(emqx_gm_subopts *so);
+
 /* ---- a whole publish window in one device round trip (gm_publish.hip) ----
  * A broker node's unit of work is a publish window, and for every message of
  * it the node needs the matched route filters, their local subscribers, one

@@ -15,6 +15,7 @@
 -export([load_retained/1, load_retained/2, match_retained/3, expire_retained/2]).
 -export([load_shared/3, load_shared/4, pick_shared/4, pick_shared_nif/5]).
 -export([publish_window/4, publish_window_nif/5]).
+-export([load_subopts/3, deliver/5]).
 -export([load_authz/1, authorize_batch/2, authz_rule/2, authz_request/3, authorize/5]).
 -export([match/2]).
 
@@ -157,6 +158,25 @@ pick_shared(Table, Msgs, Strategy, Seed) ->
                       random -> {3, []}
                   end,
     pick_shared_nif(Table, Topics, S, Hashes, Seed band 16#FFFFFFFF).
+
+%% Subscription options at dispatch (emqx_gm_subopts_build, emqx_gm_deliver).
+%% load_subopts/3: the options of emqx_broker:subscribe/3 for the pairs of the
+%% snapshot Index (from load_index/2): Opt = QoS bor (Nl bsl 2) bor (Rap bsl 3)
+%% bor (UpgradeQoS bsl 4); a pair without an entry gets DefaultOpt
+%% (?DEFAULT_SUBOPTS is 0).  The table is bound to Index and immutable.
+-spec load_subopts(reference(), [{binary(), non_neg_integer(), 0..31}], 0..31) ->
+          {ok, reference()} | {error, term()}.
+load_subopts(_Index, _Entries, _DefaultOpt) -> erlang:nif_error(nif_not_loaded).
+
+%% deliver/5: per topic, in order, {[{SubId, Byte}], Dropped}: the local
+%% deliveries of fanout_batch/2 with the byte enrich_deliver/2 would compute
+%% (QoS bor (Retain bsl 2) bor (NlFlag bsl 3)); Mode 0 marks a No-Local hit with
+%% bit 4 (the session reproduces lists:dropwhile from it), Mode 1 removes it
+%% and counts it in Dropped.  MsgFlags = PubQoS bor (Retain bsl 2) bor
+%% (RetainedHeader bsl 3); From = the publisher's SubId or 16#FFFFFFFF.
+-spec deliver(reference(), [binary()], [0..15], [non_neg_integer()], 0 | 1) ->
+          [{[{non_neg_integer(), 0..31}], non_neg_integer()}] | {error, term()}.
+deliver(_Table, _Topics, _MsgFlags, _From, _Mode) -> erlang:nif_error(nif_not_loaded).
 
 -spec pick_shared_nif(reference(), [binary()], 0..3, [non_neg_integer()], non_neg_integer()) ->
           [[{binary(), {non_neg_integer(), non_neg_integer()}}]] | {error, term()}.

@@ -39,7 +39,12 @@ typedef struct {
   emqx_gm_authz *tab;
 } gm_authz_res;
 
-static ErlNifResourceType *INDEX_RT, *RETAINED_RT, *SHARED_RT, *AUTHZ_RT;
+typedef struct {
+  emqx_gm_subopts *so; /* retains its snapshot */
+  emqx_gm_index *idx;
+} gm_subopts_res;
+
+static ErlNifResourceType *INDEX_RT, *RETAINED_RT, *SHARED_RT, *AUTHZ_RT, *SUBOPTS_RT;
 static emqx_gm_ctx *CTX;
 /* LoadInfo {coalesce, Devices}: the context's one combining queue -- the
  * windows of dirty schedulers calling at once run as one device batch
@@ -64,6 +69,12 @@ static void shared_dtor(ErlNifEnv *env, void *obj) {
   gm_shared_res *r = (gm_shared_res *)obj;
   (void)env;
   if (r->sh) emqx_gm_shared_release(r->sh);
+}
+
+static void subopts_dtor(ErlNifEnv *env, void *obj) {
+  gm_subopts_res *r = (gm_subopts_res *)obj;
+  (void)env;
+  if (r->so) emqx_gm_subopts_release(r->so);
 }
 
 static void authz_dtor(ErlNifEnv *env, void *obj) {
@@ -106,6 +117,7 @@ static int load(ErlNifEnv *env, void **priv, ERL_NIF_TERM info) {
   RETAINED_RT = enif_open_resource_type(env, NULL, "emqx_gm_retained", retained_dtor, ERL_NIF_RT_CREATE, NULL);
   SHARED_RT = enif_open_resource_type(env, NULL, "emqx_gm_shared", shared_dtor, ERL_NIF_RT_CREATE, NULL);
   AUTHZ_RT = enif_open_resource_type(env, NULL, "emqx_gm_authz", authz_dtor, ERL_NIF_RT_CREATE, NULL);
+  SUBOPTS_RT = enif_open_resource_type(env, NULL, "emqx_gm_subopts", subopts_dtor, ERL_NIF_RT_CREATE, NULL);
   A_UNDEFINED = enif_make_atom(env, "undefined");
   A_OK = enif_make_atom(env, "ok");
   A_ERROR = enif_make_atom(env, "error");
@@ -116,7 +128,9 @@ static int load(ErlNifEnv *env, void **priv, ERL_NIF_TERM info) {
   A_UNSUBSCRIBE = enif_make_atom(env, "unsubscribe");
   A_ROUTE_ADD = enif_make_atom(env, "route_add");
   A_ROUTE_DELETE = enif_make_atom(env, "route_delete");
-  if (emqx_gm_open(&o, &CTX) != EMQX_GM_OK || !INDEX_RT || !RETAINED_RT || !SHARED_RT || !AUTHZ_RT) return 1;
+  if (emqx_gm_open(&o, &CTX) != EMQX_GM_OK || !INDEX_RT || !RETAINED_RT || !SHARED_RT || !AUTHZ_RT ||
+      !SUBOPTS_RT)
+    return 1;
   if (coalesce && emqx_gm_combiner_open(CTX, NULL, &COMB) != EMQX_GM_OK) return 1;
   return 0;
 }
@@ -1130,6 +1144,133 @@ static ERL_NIF_TERM authorize_batch(ErlNifEnv *env, int argc, const ERL_NIF_TERM
   return result;
 }
 
+/* ---- subscription options at dispatch (emqx_gm_subopts_*, emqx_gm_deliver) ----
+ * load_subopts(Index, [{Filter, SubId, Opt}], DefaultOpt) -> {ok, Table}
+ * the ?SUBOPTION rows of emqx_broker:subscribe/3 (emqx_broker.erl:126-145) for
+ * the pairs of the snapshot Index (from load_index/2): Opt is QoS bor (nl bsl 2)
+ * bor (rap bsl 3) bor (upgrade_qos bsl 4); a pair without an entry gets
+ * DefaultOpt.  An entry whose pair the snapshot does not hold is an error. */
+static ERL_NIF_TERM load_subopts(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_index_res *ix;
+  gm_subopts_res *res;
+  unsigned len, i = 0, def;
+  ERL_NIF_TERM h, t, *filters, list, term;
+  uint8_t *fb, *opts;
+  uint64_t *fo, n;
+  uint32_t *subs;
+  emqx_gm_subopts *so = NULL;
+  int rc, ok = 1;
+  (void)argc;
+  if (!enif_get_resource(env, argv[0], INDEX_RT, (void **)&ix) || !enif_get_list_length(env, argv[1], &len) ||
+      !enif_get_uint(env, argv[2], &def) || def > 255)
+    return enif_make_badarg(env);
+  filters = enif_alloc(sizeof(ERL_NIF_TERM) * (len ? len : 1));
+  subs = enif_alloc(sizeof(uint32_t) * (len ? len : 1));
+  opts = enif_alloc(len ? len : 1);
+  t = argv[1];
+  while (ok && enif_get_list_cell(env, t, &h, &t)) {
+    const ERL_NIF_TERM *tup;
+    int arity;
+    unsigned s = 0, o = 0;
+    /* (an Opt or DefaultOpt with bits 5-7 or QoS 3 fits a byte here and is refused by the library) */
+    ok = enif_get_tuple(env, h, &arity, &tup) && arity == 3 && enif_get_uint(env, tup[1], &s) &&
+         enif_get_uint(env, tup[2], &o) && o <= 255;
+    if (ok) {
+      filters[i] = tup[0];
+      subs[i] = s;
+      opts[i++] = (uint8_t)o;
+    }
+  }
+  list = enif_make_list_from_array(env, filters, i);
+  enif_free(filters);
+  if (!ok || !pack_list(env, list, &fb, &fo, &n)) {
+    enif_free(subs);
+    enif_free(opts);
+    return enif_make_badarg(env);
+  }
+  rc = emqx_gm_subopts_build(CTX, ix->idx, fb, fo, subs, opts, n, (uint8_t)def, 0, &so);
+  enif_free(subs);
+  enif_free(opts);
+  enif_free(fb);
+  enif_free(fo);
+  if (rc != EMQX_GM_OK) return error_tuple(env, rc);
+  res = enif_alloc_resource(SUBOPTS_RT, sizeof(*res));
+  res->so = so;
+  res->idx = ix->idx; /* (kept alive by the table's own reference) */
+  term = enif_make_resource(env, res);
+  enif_release_resource(res);
+  return enif_make_tuple2(env, A_OK, term);
+}
+
+/* deliver(Table, [Topic], [MsgFlags], [From], Mode :: 0 | 1) -> [{[{SubId, Byte}], Dropped}]
+ * per topic, in batch order: the local deliveries of fanout_batch/2 over the
+ * table's snapshot, each with the byte emqx_session:enrich_deliver/2 would
+ * compute (QoS, retain bsl 2, nl bsl 3) -- so emqx_channel:handle_deliver/2
+ * takes the bytes instead of calling ignore_local/4 and enrich_deliver/2 per
+ * delivery.  MsgFlags: PubQoS bor (retain bsl 2) bor (retained-header bsl 3);
+ * From: the publisher's SubId, or 16#FFFFFFFF.  Mode 0 marks a No-Local hit
+ * with bit 4; Mode 1 removes it and counts it in Dropped
+ * ('delivery.dropped.no_local').  The rows are matched on the table's own
+ * snapshot, so they are always rows of the snapshot it is bound to. */
+static ERL_NIF_TERM deliver_nif(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_subopts_res *r;
+  uint8_t *tb, *mf;
+  uint64_t *to, n, i, k;
+  unsigned nf = 0, nfr = 0, mode, v = 0;
+  uint32_t *from;
+  emqx_gm_csr m;
+  emqx_gm_deliveries d;
+  ERL_NIF_TERM result, *rows, h, t;
+  int rc, ok = 1;
+  (void)argc;
+  if (!enif_get_resource(env, argv[0], SUBOPTS_RT, (void **)&r) || !enif_get_list_length(env, argv[2], &nf) ||
+      !enif_get_list_length(env, argv[3], &nfr) || !enif_get_uint(env, argv[4], &mode))
+    return enif_make_badarg(env);
+  if (!pack_topics(env, argv[1], &tb, &to, &n)) return enif_make_badarg(env);
+  if (nf != n || nfr != n) {
+    free_topics(tb, to);
+    return enif_make_badarg(env);
+  }
+  mf = enif_alloc(n ? n : 1);
+  from = enif_alloc(sizeof(uint32_t) * (n ? n : 1));
+  for (i = 0, t = argv[2]; ok && enif_get_list_cell(env, t, &h, &t); ++i) {
+    ok = enif_get_uint(env, h, &v) && v <= 255; /* (bits 4-7 and QoS 3: refused by the library) */
+    if (ok) mf[i] = (uint8_t)v;
+  }
+  for (i = 0, t = argv[3]; ok && enif_get_list_cell(env, t, &h, &t); ++i) {
+    ok = enif_get_uint(env, h, &v);
+    if (ok) from[i] = v;
+  }
+  if (!ok) {
+    enif_free(mf);
+    enif_free(from);
+    free_topics(tb, to);
+    return enif_make_badarg(env);
+  }
+  rc = emqx_gm_match(CTX, r->idx, tb, to, n, EMQX_GM_WITH_EXACT, &m);
+  free_topics(tb, to);
+  if (rc == EMQX_GM_OK) {
+    rc = emqx_gm_deliver(CTX, r->so, &m, mf, from, mode, &d);
+    emqx_gm_csr_free(CTX, &m);
+  }
+  enif_free(mf);
+  enif_free(from);
+  if (rc != EMQX_GM_OK) return error_tuple(env, rc);
+  rows = enif_alloc(sizeof(ERL_NIF_TERM) * (n ? n : 1));
+  for (i = 0; i < n; ++i) {
+    ERL_NIF_TERM row = enif_make_list(env, 0);
+    for (k = d.deliveries.row_off[i + 1]; k > d.deliveries.row_off[i]; --k)
+      row = enif_make_list_cell(
+          env, enif_make_tuple2(env, enif_make_uint(env, d.deliveries.ids[k - 1]), enif_make_uint(env, d.dopt[k - 1])),
+          row);
+    rows[i] = enif_make_tuple2(env, row, enif_make_uint(env, d.row_dropped ? d.row_dropped[i] : 0));
+  }
+  result = enif_make_list_from_array(env, rows, (unsigned)n);
+  enif_free(rows);
+  emqx_gm_deliveries_free(CTX, &d);
+  return result;
+}
+
 static ErlNifFunc funcs[] = {
     {"load_index", 1, load_index, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"load_index", 2, load_index, ERL_NIF_DIRTY_JOB_CPU_BOUND},
@@ -1151,6 +1292,8 @@ static ErlNifFunc funcs[] = {
     {"load_shared", 4, load_shared, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"pick_shared_nif", 5, pick_shared_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"publish_window_nif", 5, publish_window_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"load_subopts", 3, load_subopts, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"deliver", 5, deliver_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"load_authz", 1, load_authz, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"authorize_batch", 2, authorize_batch, ERL_NIF_DIRTY_JOB_CPU_BOUND},
 };
