@@ -136,6 +136,15 @@ class PublishStats(C.Structure):
                 ("n_pairs", C.c_uint64), ("cap_hits", C.c_uint64), ("cap_pairs", C.c_uint64)]
 
 
+class PublishDeliverOpts(C.Structure):
+    _fields_ = [("subopts", C.c_void_p), ("msg_flags", C.c_void_p), ("msg_from", C.c_void_p), ("mode", C.c_uint32)]
+
+
+class PublishDeliverStats(C.Structure):
+    _fields_ = [("window", PublishStats), ("deliveries_spec", C.c_uint8), ("n_deliveries", C.c_uint64),
+                ("n_dropped", C.c_uint64), ("cap_deliveries", C.c_uint64)]
+
+
 class PublishWin(C.Structure):
     _fields_ = [("w", Window), ("msg_hash", C.c_void_p)]
 
@@ -250,6 +259,9 @@ SIGNATURES = {
     "emqx_gm_publish_window": (_i32, [_vp, _vp, _vp, _vp, _u64, C.POINTER(PublishOpts), C.POINTER(PublishResult),
                                       C.POINTER(PublishStats)]),
     "emqx_gm_publish_result_free": (_i32, [_vp, C.POINTER(PublishResult)]),
+    "emqx_gm_publish_window_deliver": (_i32, [_vp, _vp, _vp, _vp, _u64, C.POINTER(PublishOpts),
+                                              C.POINTER(PublishDeliverOpts), C.POINTER(PublishResult),
+                                              C.POINTER(Deliveries), C.POINTER(PublishDeliverStats)]),
     "emqx_gm_publish_windows": (_i32, [_vp, _vp, C.POINTER(PublishWin), _u32, C.POINTER(PublishOpts),
                                        C.POINTER(PublishResult), C.POINTER(PublishStats),
                                        C.POINTER(PublishGroupStats)]),

@@ -250,6 +250,10 @@ class GpuRoutes:
         # FLAG mode: the deliveries are the fan-out's, so a row is cut per filter by the snapshot's own
         # counts; the device's bit 4 is the one verdict on No Local, and `drop` removes what it marks
         d = tab.deliver((ro, ids), msg_flags, msg_from, False, index=idx)
+        return self._cut_opts(idx, ro, ids, d, drop)
+
+    def _cut_opts(self, idx, ro, ids, d, drop: bool) -> List[Row]:
+        """FLAG-mode deliveries (a ``Delivered``) cut into one (filter, _IdsOpts) per matched filter."""
         out = []
         for k in range(len(ro) - 1):
             row, pos = [], int(d.row_off[k])
@@ -287,20 +291,38 @@ class GpuRoutes:
             out.append(row)
         return out
 
-    def window(self, topics: Sequence[bytes], shared=None, strategy="round_robin", hashes=None, cluster=None):
+    def window(self, topics: Sequence[bytes], shared=None, strategy="round_robin", hashes=None, cluster=None,
+               opts=None, drop: bool = False):
         """``groups_rows`` plus the window's shared picks (``shared``, a SharedSub:
         what its ``dispatch_batch`` gives, same per-call seed rule) and forward
         plan (``cluster``, a ClusterRoutes: what its ``plan`` gives) from ONE
         ``Context.publish_window`` call -- one device round trip where the three
         calls make five waits; with a combiner, ``Combiner.publish_window``: the
         same call, coalesced with the whole windows of concurrent callers.  Returns (rows, snapshot, (row_off, filter ids),
-        picks per row or None, ForwardPlan or None, stats)."""
+        picks per row or None, ForwardPlan or None, stats).
+
+        ``opts = (msg_flags, msg_from)``: the rows carry the option bytes, cut as
+        ``groups_opts`` cuts them -- ``(filter, _IdsOpts)``, FLAG mode on the
+        device, ``drop`` applied here from bit 4 -- and come from the same one
+        call (emqx_gm_publish_window_deliver: the deliveries in place of the plain
+        fan-out).  That call runs on the context directly, also when the routes
+        were built over a combiner."""
+        if opts is not None:
+            self.subopts_on = True
         self.refresh()
         if self.stale:
             raise RuntimeError("stale_index")
         idx = self.index
         st = shared.table(idx) if shared is not None else None
         dt = cluster.table(idx) if cluster is not None else None
+        if opts is not None:
+            (ro, ids), d, picks, plan, stats = self.ctx.publish_window(
+                idx, list(topics), exact=True, shared=st, strategy=strategy, hashes=hashes,
+                seed=shared.next_seed() if shared is not None else 0, dests=dt,
+                skip_node=cluster.self_id if cluster is not None else None,
+                subopts=self._so_table, msg_flags=opts[0], msg_from=opts[1], drop=False)
+            rows = self._cut_opts(idx, ro, ids, d, drop)
+            return rows, idx, (ro, ids), (shared.picks_rows(*picks) if shared is not None else None), plan, stats
         (ro, ids), (fro, fids), picks, plan, stats = (self.combiner or self.ctx).publish_window(
             idx, list(topics), exact=True, shared=st, strategy=strategy, hashes=hashes,
             seed=shared.next_seed() if shared is not None else 0, dests=dt,
@@ -358,11 +380,15 @@ class PublishBatcher:
     (emqx_gm_combiner_publish): whole windows of concurrent batchers share one
     device round trip.
 
-    ``subopts`` (needs ``routes``; not with ``shared`` / ``cluster`` yet): the
-    window's local deliveries come from ``routes.groups_opts`` (one match, one
-    emqx_gm_deliver) with the byte emqx_session:enrich_deliver/2 would compute
-    beside every subscriber id, and ``deliver`` is called as ``deliver(sub,
-    filter, msg, byte)`` (``unpack_dopt``).  ``msg_meta(topic, msg) -> (qos,
+    ``subopts`` (needs ``routes``; with ``shared`` / ``cluster`` only together
+    with ``one_call``): the window's local deliveries come from
+    ``routes.groups_opts`` (one match, one emqx_gm_deliver) with the byte
+    emqx_session:enrich_deliver/2 would compute beside every subscriber id, and
+    ``deliver`` is called as ``deliver(sub, filter, msg, byte)``
+    (``unpack_dopt``).  With ``one_call`` they come from the window call itself
+    (``routes.window(..., opts=)``, emqx_gm_publish_window_deliver: the
+    deliveries with their bytes in the window's one device round trip, beside
+    the picks and the plan); the deliveries and metrics are the same.  ``msg_meta(topic, msg) -> (qos,
     retain, from[, headers.retained])`` reads a message; ``from`` is the
     publishing subscriber as ``routes.ids`` knows it, or None.
     ``drop_no_local`` removes the deliveries the device marked as No-Local hits
@@ -404,8 +430,10 @@ class PublishBatcher:
             raise TypeError("PublishBatcher(cluster=...) needs routes (the window's matched rows)")
         if one_call and routes is None:
             raise TypeError("PublishBatcher(one_call=True) needs routes (the window call)")
-        if subopts and (routes is None or shared is not None or cluster is not None):
-            raise TypeError("PublishBatcher(subopts=True) needs routes, without shared / cluster")
+        if subopts and routes is None:
+            raise TypeError("PublishBatcher(subopts=True) needs routes")
+        if subopts and not one_call and (shared is not None or cluster is not None):
+            raise TypeError("PublishBatcher(subopts=True) with shared / cluster needs one_call=True (the window call)")
         self.subopts, self.drop_no_local, self.msg_meta = subopts, drop_no_local, msg_meta
         self.one_call = one_call
         self.routes, self.shared, self.shared_strategy = routes, shared, shared_strategy
@@ -501,15 +529,29 @@ class PublishBatcher:
                     self._cv.wait(timeout=wait)
             self.poll()
 
+    def _msg_opts(self, topics, msgs):
+        """The window's message bytes and publishers: (``pack_msg`` bytes, ``routes.ids`` ids or None)."""
+        from .subopts import pack_msg
+        meta = [tuple(self.msg_meta(t, m)) + (False,) for t, m in zip(topics, msgs)]
+        flags = [pack_msg(q, rt, hdr) for q, rt, _, hdr, *_ in meta]
+        froms = [self.routes.ids.get(frm) if frm is not None else None for _, _, frm, *_ in meta]
+        return flags, froms
+
     def _rows(self, topics: Sequence[bytes], msgs: Optional[Sequence[object]] = None):
         try:
-            if self.shared is not None or self.cluster is not None:
+            if self.shared is not None or self.cluster is not None or (self.subopts and self.one_call):
                 msgs = msgs if msgs is not None else [None] * len(topics)
                 hashes = None
                 if self.shared is not None and self.shared_strategy.startswith("hash"):
                     hashes = [self.shared_hash(t, m) & 0xFFFFFFFF for t, m in zip(topics, msgs)]
                 plan = None
-                if self.one_call:  # rows, picks and plan: one device call
+                if self.one_call and self.subopts:  # ... and the deliveries' option bytes, the same one call
+                    rows, idx, csr, picks, plan, _ = self.routes.window(
+                        list(topics), shared=self.shared, strategy=self.shared_strategy, hashes=hashes,
+                        cluster=self.cluster, opts=self._msg_opts(topics, msgs), drop=self.drop_no_local)
+                    if picks is None:
+                        picks = [None] * len(rows)
+                elif self.one_call:  # rows, picks and plan: one device call
                     rows, idx, csr, picks, plan, _ = self.routes.window(
                         list(topics), shared=self.shared, strategy=self.shared_strategy, hashes=hashes,
                         cluster=self.cluster)
@@ -524,11 +566,8 @@ class PublishBatcher:
                     return [("ok", r, p) for r, p in zip(rows, picks)]
                 return [("ok", r, p, w) for r, p, w in zip(rows, picks, self._forward_window(idx, csr, msgs, plan))]
             if self.subopts:  # the window's deliveries with their option bytes: one match, one deliver call
-                from .subopts import pack_msg
                 msgs = msgs if msgs is not None else [None] * len(topics)
-                meta = [tuple(self.msg_meta(t, m)) + (False,) for t, m in zip(topics, msgs)]
-                flags = [pack_msg(q, rt, hdr) for q, rt, _, hdr, *_ in meta]
-                froms = [self.routes.ids.get(frm) if frm is not None else None for _, _, frm, *_ in meta]
+                flags, froms = self._msg_opts(topics, msgs)
                 return [("ok", r) for r in self.routes.groups_opts(list(topics), flags, froms, self.drop_no_local)]
             return [("ok", r) for r in self.groups_fn(list(topics))]
         except Exception as e:  # the NIF's {error, _}: every caller takes the reference path

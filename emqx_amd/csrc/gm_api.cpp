@@ -17,6 +17,7 @@
 #include "gm_internal.h"
 #include "gm_publish.h"
 #include "gm_shared.h"
+#include "gm_subopts.h"
 #include "../../include/emqx_gm_ext.h"
 
 namespace gm {
@@ -829,11 +830,9 @@ int emqx_gm_publish_result_free(emqx_gm_ctx* ctx, emqx_gm_publish_result* res) {
   return EMQX_GM_OK;
 }
 
-int emqx_gm_publish_window(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to,
-                           uint64_t n, const emqx_gm_publish_opts* o, emqx_gm_publish_result* out,
-                           emqx_gm_publish_stats* stats) {
-  if (!ctx) return EMQX_GM_EINVAL;
-  // every argument checked before any device work, no output touched
+// every argument of a publish window checked before any device work, no output touched
+static int publish_window_check(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to,
+                                uint64_t n, const emqx_gm_publish_opts* o, emqx_gm_publish_result* out) {
   if (!idx || !o || !out || (n && (!tb || !to)))
     return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window: NULL argument");
   if (o->flags & ~EMQX_GM_WITH_EXACT)
@@ -860,6 +859,14 @@ int emqx_gm_publish_window(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uin
     if (dt->idx != idx)
       return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window: the dests table is bound to another snapshot");
   }
+  return EMQX_GM_OK;
+}
+
+int emqx_gm_publish_window(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to,
+                           uint64_t n, const emqx_gm_publish_opts* o, emqx_gm_publish_result* out,
+                           emqx_gm_publish_stats* stats) {
+  if (!ctx) return EMQX_GM_EINVAL;
+  if (const int crc = publish_window_check(ctx, idx, tb, to, n, o, out)) return crc;
   std::memset(out, 0, sizeof(*out));
   emqx_gm_publish_stats st{};
   int rc = EMQX_GM_OK;
@@ -907,6 +914,86 @@ int emqx_gm_publish_window(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uin
       st.n_pairs = out->forwards.n_pairs;
     }
   }
+  GM_GUARD_END(ctx)
+  if (stats) *stats = st;
+  return EMQX_GM_OK;
+}
+
+// ---- ... with the deliveries' option bytes as a third speculative part, in
+// place of the plain fan-out (gm_publish.hip, gm_subopts.hip so_queue_spec) ----
+int emqx_gm_publish_window_deliver(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to,
+                                   uint64_t n, const emqx_gm_publish_opts* o, const emqx_gm_publish_deliver_opts* d,
+                                   emqx_gm_publish_result* out, emqx_gm_deliveries* deliv,
+                                   emqx_gm_publish_deliver_stats* stats) {
+  if (!ctx) return EMQX_GM_EINVAL;
+  if (const int crc = publish_window_check(ctx, idx, tb, to, n, o, out)) return crc;
+  if (!d || !deliv || !d->subopts || (n && (!d->msg_flags || !d->msg_from)))
+    return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window_deliver: NULL argument");
+  if (d->mode != EMQX_GM_SO_FLAG && d->mode != EMQX_GM_SO_DROP)
+    return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window_deliver: mode");
+  emqx_gm_subopts* so = d->subopts;
+  if (!so->dev_base) return gm::set_err(ctx, EMQX_GM_EUNSUPPORTED, "publish_window_deliver: a host-only table");
+  if (so->device != ctx->device)
+    return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window_deliver: the table is on another device");
+  if (so->idx != idx)
+    return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window_deliver: the table is bound to another snapshot");
+  for (uint64_t r = 0; r < n; ++r)
+    if (gm::so_bad_msg(d->msg_flags[r]))
+      return gm::set_err(ctx, EMQX_GM_EINVAL, "publish_window_deliver: msg_flags[" + std::to_string(r) + "] = " +
+                                                  std::to_string(d->msg_flags[r]));
+  std::memset(out, 0, sizeof(*out));
+  std::memset(deliv, 0, sizeof(*deliv));
+  emqx_gm_publish_deliver_stats st{};
+  int rc = EMQX_GM_OK;
+  auto fail = [&](int code) {  // every output zeroed, nothing held (the failing call's message stays)
+    emqx_gm_publish_result_free(ctx, out);
+    if (deliv->deliveries.row_off || deliv->deliveries.ids || deliv->dopt || deliv->row_dropped)
+      emqx_gm_deliveries_free(ctx, deliv);
+    std::memset(deliv, 0, sizeof(*deliv));
+    return code;
+  };
+  GM_GUARD_BEGIN
+  if (small_call(idx, to, n, o->flags) && !idx->view.gmap && !idx->subs.empty() && !gm::knob("GM_FANOUT_SIMPLE")) {
+    gm::PwArgs a;
+    a.sh = o->shared;
+    a.strategy = o->strategy;
+    a.seed = o->seed;
+    a.msg_hash = o->msg_hash;
+    a.dt = o->dests;
+    a.skip_node = o->skip_node;
+    a.so = so;
+    a.msg_flags = d->msg_flags;
+    a.msg_from = d->msg_from;
+    a.so_mode = d->mode;
+    gm::PwDeliv dl;
+    emqx_gm_match_stats ms{};
+    hipSetDevice(ctx->device);
+    rc = gm::run_publish_window(ctx, idx, tb, to, n, o->flags, a, out, &st.window, &ms, nullptr, &dl);
+    if (rc != EMQX_GM_OK) return fail(rc);
+    tl_stats = ms;
+    tl_stats_ctx = ctx;
+    *deliv = dl.out;
+    st.deliveries_spec = dl.spec;
+    st.cap_deliveries = dl.cap;
+  } else {  // not a one-round-trip window: the calls in sequence (their waits are not counted)
+    rc = emqx_gm_match(ctx, idx, tb, to, n, o->flags, &out->matches);
+    if (rc != EMQX_GM_OK) return fail(rc);
+    if (o->shared) {
+      rc = emqx_gm_shared_pick(ctx, o->shared, &out->matches, o->strategy, o->msg_hash, o->seed, &out->pick_members,
+                               &out->pick_slots);
+      if (rc != EMQX_GM_OK) return fail(rc);
+      st.window.n_hits = out->pick_members.nnz;
+    }
+    if (o->dests) {
+      rc = emqx_gm_forward_plan(ctx, o->dests, &out->matches, o->skip_node, &out->forwards);
+      if (rc != EMQX_GM_OK) return fail(rc);
+      st.window.n_pairs = out->forwards.n_pairs;
+    }
+    rc = emqx_gm_deliver(ctx, so, &out->matches, d->msg_flags, d->msg_from, d->mode, deliv);
+    if (rc != EMQX_GM_OK) return fail(rc);
+  }
+  st.n_deliveries = deliv->deliveries.nnz;
+  st.n_dropped = deliv->n_dropped;
   GM_GUARD_END(ctx)
   if (stats) *stats = st;
   return EMQX_GM_OK;

@@ -12,16 +12,30 @@ struct PwArgs {
   const uint32_t* msg_hash = nullptr;  // host, one per topic (EMQX_GM_SHARE_HASH)
   emqx_gm_dests* dt = nullptr;   // nullptr: no plan
   uint32_t skip_node = 0;
+  // emqx_gm_publish_window_deliver (nullptr: the plain fan-out)
+  emqx_gm_subopts* so = nullptr;
+  const uint8_t* msg_flags = nullptr;  // host, one per topic
+  const uint32_t* msg_from = nullptr;  // host, one per topic
+  uint32_t so_mode = 0;
+};
+
+// what a window with a.so returns beside res: the deliveries with their bytes (host pool arrays)
+struct PwDeliv {
+  emqx_gm_deliveries out{};
+  bool spec = false;  // they came from the first round trip
+  uint64_t cap = 0;   // the speculative capacity used (0: not speculated)
 };
 
 // A window run_host_small serves, whole on ctx's device (entered WITHOUT
 // ctx->mu): the match, its fan-out (fan, as run_host_small's), the picks and the
 // plan in one device round trip where the speculation holds.  res->deliveries
-// is left to the caller (fan->ok: fan->out).  On an error nothing is held and
-// the shared table's state is unchanged.
+// is left to the caller (fan->ok: fan->out).  With a.so the deliveries with
+// their option bytes run as a third part in place of the fan-out (fan is not
+// used) and come back in dl.  On an error nothing is held and the shared
+// table's state is unchanged.
 int run_publish_window(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to, uint64_t n,
                        uint32_t flags, const PwArgs& a, emqx_gm_publish_result* res, emqx_gm_publish_stats* st_out,
-                       emqx_gm_match_stats* mst, SmallFan* fan);
+                       emqx_gm_match_stats* mst, SmallFan* fan, PwDeliv* dl = nullptr);
 
 // A GROUP of such windows as one device batch (emqx_gm_publish_windows; entered
 // WITHOUT ctx->mu; the caller has checked what run_host_windows asks for): one

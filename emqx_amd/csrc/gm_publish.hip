@@ -23,6 +23,13 @@
 //           fits its capacity; a held pick queues k_sh_commit (no wait).  A part
 //           that does not hold is run again at its exact size on the device
 //           rows (sh_pick_device / dt_plan_device, host_out).
+// emqx_gm_publish_window_deliver: the deliveries with their option bytes are a
+// THIRD speculative part, in place of the plain fan-out (gm_subopts.hip
+// so_queue_spec into cap_deliveries entries, k_so_pack: one more copy-out
+// launch).  finish() settles them after the plan and before the picks'
+// commit, so the shared state is unchanged on every error of the call; a part
+// that does not hold: so_deliver_device (host_out) on the device rows and the
+// messages already uploaded.
 // Capacities: the fan-out's rule -- 1024 + the ids past the slack x this
 // context's recent hits (pairs) per match, rounded up to a power of two.
 //
@@ -39,6 +46,7 @@
 #include "gm_dests.h"
 #include "gm_publish.h"
 #include "gm_shared.h"
+#include "gm_subopts.h"
 
 namespace gm {
 namespace {
@@ -133,18 +141,23 @@ struct PwStage {
   const PwArgs& a;
   uint64_t n;
   emqx_gm_publish_stats st{};
-  bool q_pick = false, q_plan = false;
+  bool q_pick = false, q_plan = false, q_del = false, del_spec = false;
   ShSpec ps;
   DtSpec fs;
+  SoSpec ds;
   void* d_hash = nullptr;
-  uint64_t cap_hits = 0, cap_pairs = 0;
+  uint64_t cap_hits = 0, cap_pairs = 0, cap_del = 0;
   // the page-locked results of the speculative run
   uint64_t* h_pro[2] = {nullptr, nullptr};
   uint64_t *h_noff = nullptr, *h_meta = nullptr;
   uint32_t *h_mem = nullptr, *h_slot = nullptr, *h_rows = nullptr, *h_fil = nullptr, *h_rr = nullptr;
+  uint64_t *h_dro = nullptr, *h_dmeta = nullptr;
+  uint32_t *h_dids = nullptr, *h_drd = nullptr;
+  uint8_t* h_dopt = nullptr;
   // what the call returns
   emqx_gm_csr members{}, slots{};
   emqx_gm_forwards fw{};
+  emqx_gm_deliveries deliv{};
 
   PwStage(emqx_gm_ctx* c, const PwArgs& args, uint64_t n_topics) : ctx(c), a(args), n(n_topics) {}
 
@@ -166,22 +179,37 @@ struct PwStage {
     h_noff = nullptr;
     h_rows = h_fil = h_rr = nullptr;
   }
+  void drop_del_host() {
+    for (void* p : {static_cast<void*>(h_dro), static_cast<void*>(h_dids), static_cast<void*>(h_dopt),
+                    static_cast<void*>(h_drd)})
+      ctx->hpool->release(p);
+    h_dro = nullptr;
+    h_dids = h_drd = nullptr;
+    h_dopt = nullptr;
+  }
   void drop_device() {  // the workspaces back to the pool behind the work queued so far
-    void* ps3[3] = {ps.ws, fs.ws, d_hash};
-    for (void* p : ps3)
+    void* ps4[4] = {ps.ws, fs.ws, d_hash, ds.ws};
+    for (void* p : ps4)
       if (p) ctx->pool->release_after(p, ctx->stream);
     ps = ShSpec{};
     fs = DtSpec{};
+    ds = SoSpec{};
     d_hash = nullptr;
-    q_pick = q_plan = false;
+    q_pick = q_plan = q_del = false;
   }
   // a failed call: nothing is held
   void drop_all() {
     drop_device();
     drop_pick_host();
     drop_plan_host();
+    drop_del_host();
     ctx->hpool->release(h_meta);
-    h_meta = nullptr;
+    ctx->hpool->release(h_dmeta);
+    h_meta = h_dmeta = nullptr;
+    for (void* p : {static_cast<void*>(deliv.deliveries.row_off), static_cast<void*>(deliv.deliveries.ids),
+                    static_cast<void*>(deliv.dopt), static_cast<void*>(deliv.row_dropped)})
+      ctx->hpool->release(p);
+    deliv = emqx_gm_deliveries{};
     for (emqx_gm_csr* c : {&members, &slots}) {
       ctx->hpool->release(c->row_off);
       ctx->hpool->release(c->ids);
@@ -193,8 +221,29 @@ struct PwStage {
     fw = emqx_gm_forwards{};
   }
 
-  void queue(const uint64_t* d_ro, const uint32_t* d_ids, uint64_t cap, const uint32_t* hash_pin) {
+  // the deliveries with their option bytes: the fan-out's own capacity and rule, one copy-out launch of their own
+  void queue_deliv(const uint64_t* d_ro, const uint32_t* d_ids, uint64_t cap, const void* msgs_pin) {
+    if (!a.so || !n || !(cap_del = spec_cap(so_cap_knob(), cap, ctx->subs_per_match))) return;
+    if (so_queue_spec(ctx, a.so, d_ro, d_ids, n, cap, cap_del, a.so_mode, msgs_pin, &ds)) return;
+    const bool drop = a.so_mode == EMQX_GM_SO_DROP;
+    h_dmeta = static_cast<uint64_t*>(ctx->hpool->alloc(64, true));
+    h_dro = static_cast<uint64_t*>(ctx->hpool->alloc((n + 1) * 8, true));
+    h_dids = static_cast<uint32_t*>(ctx->hpool->alloc(pow2_bytes(cap_del), true));
+    h_dopt = static_cast<uint8_t*>(ctx->hpool->alloc(pow2_bytes((cap_del + 3) / 4), true));
+    if (drop) h_drd = static_cast<uint32_t*>(ctx->hpool->alloc(std::max<size_t>(n * 4, 16), true));
+    uint64_t *o_meta = dev_ptr(h_dmeta), *o_ro = dev_ptr(h_dro);
+    uint32_t *o_ids = dev_ptr(h_dids), *o_rd = drop ? dev_ptr(h_drd) : nullptr;
+    uint8_t* o_opt = dev_ptr(h_dopt);
+    // (no room, or nothing comes back: this part runs after the wait, on the messages already up)
+    q_del = o_meta && o_ro && o_ids && o_opt && (!drop || o_rd) &&
+            so_queue_pack(ctx, ds, n, cap_del, o_ro, o_ids, o_opt, o_rd, o_meta) == 0;
+    if (!q_del) drop_del_host();
+  }
+
+  void queue(const uint64_t* d_ro, const uint32_t* d_ids, uint64_t cap, const uint32_t* hash_pin,
+             const void* msgs_pin) {
     hipStream_t s = ctx->stream;
+    queue_deliv(d_ro, d_ids, cap, msgs_pin);
     const uint32_t N = a.dt ? a.dt->hv.n_nodes : 0;
     if (a.sh && (cap_hits = spec_cap(knob("GM_PW_CAP_HITS"), cap, ctx->hits_per_match))) {
       bool ok = true;
@@ -301,6 +350,33 @@ struct PwStage {
       st.n_pairs = fw.n_pairs;
       if (rows_spec && rows->nnz) ctx->pairs_per_match = std::max(1.0 / 64, double(fw.n_pairs) / double(rows->nnz));
     }
+    // the deliveries: settled before the picks' commit
+    if (a.so) {
+      const uint64_t tot = h_dmeta ? h_dmeta[0] : 0, dropped = h_dmeta ? h_dmeta[1] : 0;
+      if (q_del && rows_spec && tot <= cap_del) {
+        deliv.deliveries.n_rows = n;
+        deliv.deliveries.nnz = tot;
+        deliv.deliveries.row_off = h_dro;
+        deliv.deliveries.ids = h_dids;
+        deliv.deliveries.on_device = 0;
+        deliv.deliveries.priv = ctx;
+        deliv.dopt = h_dopt;
+        deliv.row_dropped = h_drd;  // (nullptr in FLAG mode)
+        deliv.n_dropped = dropped;
+        h_dro = nullptr;
+        h_dids = h_drd = nullptr;
+        h_dopt = nullptr;
+        del_spec = true;
+      } else {
+        drop_del_host();
+        rc = so_deliver_device(ctx, a.so, rows, a.msg_flags, a.msg_from, a.so_mode, &deliv, true, &st.device_waits,
+                               ds.d_flags, ds.d_from);
+        if (rc) return rc;
+      }
+      // (the plain fan-out's figure, whichever kind of window ran last)
+      if (rows_spec && rows->nnz)
+        ctx->subs_per_match = std::max(1.0, double(deliv.deliveries.nnz + deliv.n_dropped) / double(rows->nnz));
+    }
     if (a.sh) {
       if (q_pick && rows_spec && hits <= cap_hits) {
         emqx_gm_csr* outs[2] = {&members, &slots};
@@ -332,7 +408,8 @@ struct PwStage {
     }
     drop_device();
     ctx->hpool->release(h_meta);
-    h_meta = nullptr;
+    ctx->hpool->release(h_dmeta);
+    h_meta = h_dmeta = nullptr;
     return EMQX_GM_OK;
   }
 };
@@ -810,8 +887,21 @@ int run_publish_windows(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const emqx_g
 
 int run_publish_window(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t* tb, const uint64_t* to, uint64_t n,
                        uint32_t flags, const PwArgs& a, emqx_gm_publish_result* res, emqx_gm_publish_stats* st_out,
-                       emqx_gm_match_stats* mst, SmallFan* fan) {
+                       emqx_gm_match_stats* mst, SmallFan* fan, PwDeliv* dl) {
   PwStage stage(ctx, a, n);
+  // the messages' flags and publishers likewise: [publishers | flags], up in one launch
+  PinBuf mpin(ctx->pins);
+  if (a.so && n) {
+    fan = nullptr;  // (the deliveries run in place of the plain fan-out)
+    if ((mpin.p = ctx->pins->get(so_msgs_bytes(n)))) {
+      uint8_t* mp = static_cast<uint8_t*>(mpin.p);
+      std::memset(mp, 0, so_msgs_bytes(n));
+      std::memcpy(mp, a.msg_from, n * 4);
+      std::memcpy(mp + al16(n * 4), a.msg_flags, n);
+    }
+  } else if (a.so) {
+    fan = nullptr;
+  }
   // the hashes in a page-locked copy of the call's own (staged outside the lock, like the topics)
   PinBuf hpin(ctx->pins);
   if (a.sh && a.strategy == EMQX_GM_SHARE_HASH && n) {
@@ -819,7 +909,7 @@ int run_publish_window(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t
   }
   SmallSide side;
   side.queue = [&](const uint64_t* d_ro, const uint32_t* d_ids, uint64_t cap) {
-    stage.queue(d_ro, d_ids, cap, static_cast<const uint32_t*>(hpin.p));
+    stage.queue(d_ro, d_ids, cap, static_cast<const uint32_t*>(hpin.p), mpin.p);
   };
   side.finish = [&](bool rows_spec, const emqx_gm_csr* rows) { return stage.finish(rows_spec, rows); };
   // the table's own serialisation from the moment the stage is queued until the
@@ -832,9 +922,15 @@ int run_publish_window(emqx_gm_ctx* ctx, const emqx_gm_index* idx, const uint8_t
   const int rc = run_host_small(ctx, idx, tb, to, n, flags, &m, mst, fan, &side);
   if (rc) {
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (stage.q_pick || stage.q_plan) hipStreamSynchronize(ctx->stream);  // (a queued kernel may still write the results)
+    if (stage.q_pick || stage.q_plan || stage.q_del || stage.ds.ws)
+      hipStreamSynchronize(ctx->stream);  // (a queued kernel may still write the results)
     stage.drop_all();
     return rc;
+  }
+  if (dl) {
+    dl->out = stage.deliv;
+    dl->spec = stage.del_spec;
+    dl->cap = stage.cap_del;
   }
   res->matches = m;
   res->pick_members = stage.members;

@@ -20,7 +20,7 @@ namespace gm {
 
 namespace {
 bool bad_opt(uint8_t o) { return (o & 3u) == 3u || (o & 0xE0u); }
-bool bad_msg(uint8_t b) { return (b & 3u) == 3u || (b & 0xF0u); }
+bool bad_msg(uint8_t b) { return gm::so_bad_msg(b); }
 std::string shown(const uint8_t* p, uint64_t len) {
   return std::string(reinterpret_cast<const char*>(p), std::min<uint64_t>(len, 200));
 }

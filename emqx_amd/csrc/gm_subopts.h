@@ -125,6 +125,37 @@ int so_deliver_host(const emqx_gm_subopts* so, const emqx_gm_csr* m, const uint8
 // gm_subopts.hip (device)
 int so_upload(emqx_gm_ctx* ctx, emqx_gm_subopts* so);
 void so_free_device(emqx_gm_subopts* so);
+// host_out: device rows in, but the messages and the result on the host (a
+// publish window's rerun); d_flags_up / d_from_up (optional, with host_out): the
+// messages already on the device; waits (optional): += the host-blocking
+// device waits made
 int so_deliver_device(emqx_gm_ctx* ctx, emqx_gm_subopts* so, const emqx_gm_csr* m, const uint8_t* msg_flags,
-                      const uint32_t* msg_from, uint32_t mode, emqx_gm_deliveries* out);
+                      const uint32_t* msg_from, uint32_t mode, emqx_gm_deliveries* out, bool host_out = false,
+                      uint32_t* waits = nullptr, const uint8_t* d_flags_up = nullptr,
+                      const uint32_t* d_from_up = nullptr);
+// a bad message byte (so_check_call's rule)
+inline bool so_bad_msg(uint8_t b) { return (b & 3u) == 3u || (b & 0xF0u); }
+// the A/B knob of a publish window's speculative deliveries capacity (as given; "0": not speculated)
+inline const char* so_cap_knob() { return knob("GM_PW_CAP_DELIVERIES"); }
+// A window's messages as one page-locked block: [publishers n x u32 | flags n x u8], each part 16-B aligned
+inline size_t so_msgs_bytes(uint64_t n) { return al16(al16(n * 4) + n); }
+// Deliveries queued over a small call's speculative rows
+// (emqx_gm_publish_window_deliver): device pointers into one workspace `ws` of
+// the context's pool, which the caller releases behind the stream; *total is
+// the true (post-drop) delivery count, *dropped the true dropped count.
+struct SoSpec {
+  void* ws = nullptr;
+  uint64_t* row_off = nullptr;      // [n + 1]
+  uint32_t* ids = nullptr;          // [cap_d] + 16 B
+  uint8_t* dopt = nullptr;          // [cap_d] + 16 B
+  uint32_t* row_dropped = nullptr;  // [n], EMQX_GM_SO_DROP
+  const uint64_t* total = nullptr;
+  const uint64_t* dropped = nullptr;  // EMQX_GM_SO_DROP
+  const uint8_t* d_flags = nullptr;   // the uploaded messages (a rerun reads them)
+  const uint32_t* d_from = nullptr;
+};
+int so_queue_spec(emqx_gm_ctx* ctx, emqx_gm_subopts* so, const uint64_t* d_ro, const uint32_t* d_ids, uint64_t n,
+                  uint64_t cap, uint64_t cap_d, uint32_t mode, const void* msgs, SoSpec* out);
+int so_queue_pack(emqx_gm_ctx* ctx, const SoSpec& run, uint64_t n, uint64_t cap_d, uint64_t* o_ro, uint32_t* o_ids,
+                  uint8_t* o_opt, uint32_t* o_rd, uint64_t* o_meta);
 }  // namespace gm

@@ -20,6 +20,13 @@
 // No atomics, no sort, no compaction pass: a dropped delivery is skipped by
 // the source index (t + 1 from the hit on), so the output order is the
 // fan-out's.
+//
+// A publish window (emqx_gm_publish_window_deliver, gm_publish.hip) queues the
+// same kernels over its SPECULATIVE rows without the read back (so_queue_spec):
+// k_so_seglen / k_so_rowdrop over the ids' capacity with the rows' own count
+// read on the device, k_so_copy over a capacity of deliveries, and k_so_pack,
+// one launch that carries the result and the two true totals to mapped
+// page-locked buffers.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,12 +48,22 @@ __device__ __forceinline__ uint64_t so_row_of(const uint64_t* __restrict__ m_off
   return lo;
 }
 
+// nnz_p (optional, a publish window's speculative rows: nnz is their ids'
+// capacity): the rows' own count on the device; an entry past it is an empty
+// segment without a hit -- its id, its row and the table are not read (the
+// buffer's tail is uninitialised pool memory)
 __global__ __launch_bounds__(256) void k_so_seglen(SoView v, const uint64_t* __restrict__ m_off, uint64_t n_rows,
                                                    const uint32_t* __restrict__ m_ids, uint64_t nnz,
+                                                   const uint64_t* __restrict__ nnz_p,
                                                    const uint32_t* __restrict__ from, bool drop,
                                                    uint64_t* __restrict__ seg_len, uint32_t* __restrict__ seg_hit) {
   const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (i >= nnz) return;
+  if (nnz_p && i >= *nnz_p) {
+    seg_hit[i] = SO_NONE;
+    seg_len[i] = 0;
+    return;
+  }
   const uint32_t f = m_ids[i];
   uint64_t len = 0;
   uint32_t hit = SO_NONE;
@@ -75,11 +92,14 @@ __global__ __launch_bounds__(256) void k_so_seglen(SoView v, const uint64_t* __r
 }
 
 // DROP mode: the hits of a row's entries (a row holds few matched filters)
+// nnz_p (optional): as k_so_seglen's -- the offsets are clamped to the device's count too
 __global__ __launch_bounds__(256) void k_so_rowdrop(const uint64_t* __restrict__ m_off, uint64_t n_rows, uint64_t nnz,
+                                                    const uint64_t* __restrict__ nnz_p,
                                                     const uint32_t* __restrict__ seg_hit,
                                                     uint32_t* __restrict__ row_dropped) {
   const uint64_t r = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (r >= n_rows) return;
+  if (nnz_p) nnz = min(nnz, *nnz_p);
   uint64_t a = m_off[r], b = m_off[r + 1];
   if (a > nnz) a = nnz;  // (a device row offset past the ids is clamped)
   if (b > nnz) b = nnz;
@@ -211,6 +231,48 @@ __global__ __launch_bounds__(256) void k_so_copy(SoView v, const uint64_t* __res
   }
 }
 
+// A publish window's speculative deliveries to their mapped page-locked result
+// in one launch (as gm_publish.hip's k_pw_pack for the picks and the plan):
+// plain vector stores, no atomics; the ids' and bytes' lengths are the device's
+// own total clamped to the capacity, and the two true totals travel along.
+struct SoPack {
+  const uint64_t* ro;  // [n_ro] row offsets
+  uint64_t* o_ro;
+  uint64_t n_ro;
+  const uint32_t* ids;  // [cap] + slack
+  uint32_t* o_ids;
+  const uint32_t* opt;  // [cap] bytes + slack, moved as words
+  uint32_t* o_opt;
+  uint64_t cap;
+  const uint32_t* rd;  // [n_rd] DROP mode (n_rd = 0: none)
+  uint32_t* o_rd;
+  uint64_t n_rd;
+  const uint64_t *total, *dropped;  // (dropped: nullptr in FLAG mode)
+  uint64_t* o_meta;                 // [0] the true deliveries, [1] the true dropped
+};
+
+// n u32 words, 16 B at a time (every buffer here is 16-B aligned)
+__device__ __forceinline__ void so_pack_copy(uint32_t* __restrict__ d, const uint32_t* __restrict__ s, uint64_t n,
+                                             uint64_t t, uint64_t stride) {
+  const uint64_t q = n / 4;
+  for (uint64_t i = t; i < q; i += stride) reinterpret_cast<uint4*>(d)[i] = reinterpret_cast<const uint4*>(s)[i];
+  if (t < (n & 3)) d[q * 4 + t] = s[q * 4 + t];
+}
+
+__global__ __launch_bounds__(256) void k_so_pack(SoPack a) {
+  const uint64_t t = uint64_t(blockIdx.x) * 256u + threadIdx.x, stride = uint64_t(gridDim.x) * 256u;
+  const uint64_t total = *a.total, k = min(total, a.cap);
+  so_pack_copy(reinterpret_cast<uint32_t*>(a.o_ro), reinterpret_cast<const uint32_t*>(a.ro), a.n_ro * 2, t, stride);
+  so_pack_copy(a.o_ids, a.ids, k, t, stride);
+  so_pack_copy(a.o_opt, a.opt, (k + 3) / 4, t, stride);  // (the bytes' buffers end in 16 B of slack)
+  if (a.n_rd) so_pack_copy(a.o_rd, a.rd, a.n_rd, t, stride);
+  if (t == 0) {
+    a.o_meta[0] = total;
+    a.o_meta[1] = a.dropped ? *a.dropped : 0;
+  }
+  __threadfence_system();  // (host-bound stores visible before the call's end event)
+}
+
 inline uint32_t blocks_of(uint64_t n) { return uint32_t((n + 255) / 256); }
 
 struct SoUndo {  // a failing call hands back no buffers
@@ -252,10 +314,17 @@ void so_free_device(emqx_gm_subopts* so) {
 }
 
 int so_deliver_device(emqx_gm_ctx* ctx, emqx_gm_subopts* so, const emqx_gm_csr* m, const uint8_t* msg_flags,
-                      const uint32_t* msg_from, uint32_t mode, emqx_gm_deliveries* out) {
+                      const uint32_t* msg_from, uint32_t mode, emqx_gm_deliveries* out, bool host_out, uint32_t* waits,
+                      const uint8_t* d_flags_up, const uint32_t* d_from_up) {
   GM_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const bool dev = m->on_device != 0, drop = mode == EMQX_GM_SO_DROP;
+  // (host_out: device rows, but host messages -- or their uploaded copies -- and a host result: a publish
+  // window's rerun, gm_publish.hip)
+  const bool dev_in = m->on_device != 0, dev = dev_in && !host_out, drop = mode == EMQX_GM_SO_DROP;
+  const bool msgs_up = host_out && d_flags_up && d_from_up;
+  auto waited = [&]() {
+    if (waits) ++*waits;
+  };
   const uint64_t n = m->n_rows, nnz = m->nnz;
   auto res_alloc = [&](size_t bytes) -> void* {
     bytes = std::max<size_t>(bytes, 16);
@@ -292,18 +361,24 @@ int so_deliver_device(emqx_gm_ctx* ctx, emqx_gm_subopts* so, const emqx_gm_csr* 
   const uint32_t* d_mids = m->ids;
   const uint8_t* d_mf = msg_flags;
   const uint32_t* d_from = msg_from;
-  if (!dev) {
+  if (!dev_in) {
     b_ro = PoolBuf(ctx->pool, (n + 1) * 8);
     b_ids = PoolBuf(ctx->pool, nnz * 4);
-    b_mf = PoolBuf(ctx->pool, n);
-    b_from = PoolBuf(ctx->pool, n * 4);
-    if (!b_ro.p || !b_ids.p || !b_mf.p || !b_from.p) return set_err(ctx, EMQX_GM_ENOMEM, "deliver: device buffers");
+    if (!b_ro.p || !b_ids.p) return set_err(ctx, EMQX_GM_ENOMEM, "deliver: device buffers");
     GM_HIP(ctx, hipMemcpyAsync(b_ro.p, m->row_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
     GM_HIP(ctx, hipMemcpyAsync(b_ids.p, m->ids, nnz * 4, hipMemcpyHostToDevice, st));
-    GM_HIP(ctx, hipMemcpyAsync(b_mf.p, msg_flags, n, hipMemcpyHostToDevice, st));
-    GM_HIP(ctx, hipMemcpyAsync(b_from.p, msg_from, n * 4, hipMemcpyHostToDevice, st));
     d_mro = b_ro.as<uint64_t>();
     d_mids = b_ids.as<uint32_t>();
+  }
+  if (msgs_up) {
+    d_mf = d_flags_up;
+    d_from = d_from_up;
+  } else if (!dev) {
+    b_mf = PoolBuf(ctx->pool, n);
+    b_from = PoolBuf(ctx->pool, n * 4);
+    if (!b_mf.p || !b_from.p) return set_err(ctx, EMQX_GM_ENOMEM, "deliver: device buffers");
+    GM_HIP(ctx, hipMemcpyAsync(b_mf.p, msg_flags, n, hipMemcpyHostToDevice, st));
+    GM_HIP(ctx, hipMemcpyAsync(b_from.p, msg_from, n * 4, hipMemcpyHostToDevice, st));
     d_mf = b_mf.as<uint8_t>();
     d_from = b_from.as<uint32_t>();
   }
@@ -324,14 +399,15 @@ int so_deliver_device(emqx_gm_ctx* ctx, emqx_gm_subopts* so, const emqx_gm_csr* 
   EventSet<4> ev;
   if (const int rc = ev.create(ctx)) return rc;
   GM_HIP(ctx, hipEventRecord(ev.e[0], st));
-  hipLaunchKernelGGL(k_so_seglen, dim3(blocks_of(nnz)), dim3(256), 0, st, so->dv, d_mro, n, d_mids, nnz, d_from, drop,
-                     d_len.as<uint64_t>(), d_hit.as<uint32_t>());
+  hipLaunchKernelGGL(k_so_seglen, dim3(blocks_of(nnz)), dim3(256), 0, st, so->dv, d_mro, n, d_mids, nnz,
+                     static_cast<const uint64_t*>(nullptr), d_from, drop, d_len.as<uint64_t>(), d_hit.as<uint32_t>());
   GM_HIP(ctx, hipGetLastError());
   if (const int rc = scan_lengths(ctx, d_len.as<uint64_t>(), nnz, d_dst.as<uint64_t>())) return rc;
   if (launch_fanout_rowoff(st, d_mro, n, d_dst.as<uint64_t>(), o_ro, nnz))
     return set_err(ctx, EMQX_GM_EDEVICE, "deliver: row offsets");
   if (drop) {
-    hipLaunchKernelGGL(k_so_rowdrop, dim3(blocks_of(n)), dim3(256), 0, st, d_mro, n, nnz, d_hit.as<uint32_t>(), o_rd);
+    hipLaunchKernelGGL(k_so_rowdrop, dim3(blocks_of(n)), dim3(256), 0, st, d_mro, n, nnz,
+                       static_cast<const uint64_t*>(nullptr), d_hit.as<uint32_t>(), o_rd);
     GM_HIP(ctx, hipGetLastError());
     if (const int rc = scan_excl(ctx, LoadU32{o_rd}, n, d_rdsum.as<uint64_t>())) return rc;
   }
@@ -340,6 +416,7 @@ int so_deliver_device(emqx_gm_ctx* ctx, emqx_gm_subopts* so, const emqx_gm_csr* 
   GM_HIP(ctx, hipMemcpyAsync(&total, d_dst.as<uint64_t>() + nnz, 8, hipMemcpyDeviceToHost, st));
   if (drop) GM_HIP(ctx, hipMemcpyAsync(&n_dropped, d_rdsum.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
   GM_HIP(ctx, hipStreamSynchronize(st));
+  waited();
   res.deliveries.nnz = total;
   res.n_dropped = n_dropped;
   res.deliveries.ids = static_cast<uint32_t*>(res_alloc(total * 4 + 16));
@@ -372,6 +449,7 @@ int so_deliver_device(emqx_gm_ctx* ctx, emqx_gm_subopts* so, const emqx_gm_csr* 
   }
   GM_HIP(ctx, hipEventRecord(ev.e[3], st));
   GM_HIP(ctx, hipStreamSynchronize(st));
+  waited();
   float ms[3] = {0, 0, 0};
   GM_HIP(ctx, hipEventElapsedTime(&ms[0], ev.e[0], ev.e[1]));
   GM_HIP(ctx, hipEventElapsedTime(&ms[1], ev.e[1], ev.e[2]));
@@ -383,6 +461,109 @@ int so_deliver_device(emqx_gm_ctx* ctx, emqx_gm_subopts* so, const emqx_gm_csr* 
   undo.armed = false;
   *out = res;
   return EMQX_GM_OK;
+}
+
+// The deliveries of a small call's SPECULATIVE rows (gm_publish.hip), queued on
+// the context stream with no wait and no read-back: the lengths run over the
+// ids' capacity `cap` with the rows' own count read on the device (d_ro + n),
+// the copy over cap_d output elements (k_so_copy clamps to the device's total).
+// msgs: the call's page-locked [publishers | flags] (so_msgs_bytes), up in one
+// launch.  1: not queued.
+int so_queue_spec(emqx_gm_ctx* ctx, emqx_gm_subopts* so, const uint64_t* d_ro, const uint32_t* d_ids, uint64_t n,
+                  uint64_t cap, uint64_t cap_d, uint32_t mode, const void* msgs, SoSpec* out) {
+  hipStream_t st = ctx->stream;
+  if (!n || !cap || !cap_d || !msgs || !so->hv.n_subs) return 1;  // (the exact call answers without device work)
+  const bool drop = mode == EMQX_GM_SO_DROP;
+  // one workspace: messages | len | hit | dst | row offsets | row drops | their scan | ids | bytes
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += align_up(std::max<size_t>(bytes, 16), 256);
+    return at;
+  };
+  const size_t o_from = take(so_msgs_bytes(n)), o_flags = o_from + al16(n * 4);
+  const size_t o_len = take(cap * 8), o_hit = take(cap * 4), o_dst = take((cap + 1) * 8), o_ro = take((n + 1) * 8);
+  const size_t o_rd = drop ? take(n * 4) : 0, o_rds = drop ? take((n + 1) * 8) : 0;
+  const size_t o_ids = take(cap_d * 4 + 16), o_opt = take(cap_d + 16);
+  uint8_t* w = static_cast<uint8_t*>(ctx->pool->alloc(o));
+  if (!w) return 1;
+  uint64_t* len = reinterpret_cast<uint64_t*>(w + o_len);
+  uint32_t* hit = reinterpret_cast<uint32_t*>(w + o_hit);
+  uint64_t* dst = reinterpret_cast<uint64_t*>(w + o_dst);
+  out->ws = w;
+  out->d_from = reinterpret_cast<uint32_t*>(w + o_from);
+  out->d_flags = w + o_flags;
+  out->row_off = reinterpret_cast<uint64_t*>(w + o_ro);
+  out->ids = reinterpret_cast<uint32_t*>(w + o_ids);
+  out->dopt = w + o_opt;
+  out->row_dropped = drop ? reinterpret_cast<uint32_t*>(w + o_rd) : nullptr;
+  out->total = dst + cap;
+  out->dropped = drop ? reinterpret_cast<uint64_t*>(w + o_rds) + n : nullptr;
+  auto fail = [&](int rc) {
+    hipStreamSynchronize(st);  // (a queued kernel may still write the workspace)
+    ctx->pool->release(w);
+    *out = SoSpec{};
+    return rc;
+  };
+#define SO_Q(expr)                                                                                   \
+  do {                                                                                               \
+    if ((expr) != hipSuccess) return fail(set_err(ctx, EMQX_GM_EDEVICE, "publish_window: " #expr)); \
+  } while (0)
+  // the publishers and the flags (padded to words) up in ONE launch
+  void* mdev = nullptr;
+  if (so_msgs_bytes(n) <= (size_t(1) << 20) && hipHostGetDevicePointer(&mdev, const_cast<void*>(msgs), 0) == hipSuccess) {
+    const uint8_t* md = static_cast<const uint8_t*>(mdev);
+    if (launch_copy_u32x2(st, reinterpret_cast<const uint32_t*>(md), reinterpret_cast<uint32_t*>(w + o_from), n,
+                          reinterpret_cast<const uint32_t*>(md + al16(n * 4)), reinterpret_cast<uint32_t*>(w + o_flags),
+                          (n + 3) / 4))
+      return fail(set_err(ctx, EMQX_GM_EDEVICE, "publish_window: messages to device"));
+  } else {
+    SO_Q(hipMemcpyAsync(w + o_from, msgs, so_msgs_bytes(n), hipMemcpyHostToDevice, st));
+  }
+  hipLaunchKernelGGL(k_so_seglen, dim3(blocks_of(cap)), dim3(256), 0, st, so->dv, d_ro, n, d_ids, cap, d_ro + n,
+                     out->d_from, drop, len, hit);
+  SO_Q(hipGetLastError());
+  if (const int rc = scan_lengths(ctx, len, cap, dst)) return fail(rc);
+  if (launch_fanout_rowoff(st, d_ro, n, dst, out->row_off, cap))
+    return fail(set_err(ctx, EMQX_GM_EDEVICE, "publish_window: delivery row offsets"));
+  if (drop) {
+    hipLaunchKernelGGL(k_so_rowdrop, dim3(blocks_of(n)), dim3(256), 0, st, d_ro, n, cap, d_ro + n, hit,
+                       out->row_dropped);
+    SO_Q(hipGetLastError());
+    if (const int rc = scan_excl(ctx, LoadU32{out->row_dropped}, n, reinterpret_cast<uint64_t*>(w + o_rds)))
+      return fail(rc);
+  }
+  // the small fan-out's cut: 1,024 output elements a workgroup at the least
+  const uint64_t per = fan_per_block(cap_d);
+  hipLaunchKernelGGL(k_so_copy, dim3((cap_d + per - 1) / per), dim3(256), 0, st, so->dv, dst, cap, d_ro, n, d_ids, hit,
+                     out->d_flags, cap_d, per, drop, out->ids, out->dopt);
+  SO_Q(hipGetLastError());
+#undef SO_Q
+  return 0;
+}
+
+// the queued deliveries to their mapped page-locked result (device addresses), one launch
+int so_queue_pack(emqx_gm_ctx* ctx, const SoSpec& run, uint64_t n, uint64_t cap_d, uint64_t* o_ro, uint32_t* o_ids,
+                  uint8_t* o_opt, uint32_t* o_rd, uint64_t* o_meta) {
+  SoPack k{};
+  k.ro = run.row_off;
+  k.o_ro = o_ro;
+  k.n_ro = n + 1;
+  k.ids = run.ids;
+  k.o_ids = o_ids;
+  k.opt = reinterpret_cast<const uint32_t*>(run.dopt);
+  k.o_opt = reinterpret_cast<uint32_t*>(o_opt);
+  k.cap = cap_d;
+  k.rd = run.row_dropped;
+  k.o_rd = o_rd;
+  k.n_rd = run.row_dropped ? n : 0;
+  k.total = run.total;
+  k.dropped = run.dropped;
+  k.o_meta = o_meta;
+  const uint64_t words = std::max((n + 1) * 2, cap_d);
+  const uint64_t g = std::min<uint64_t>(1024, ((words + 3) / 4 + 255) / 256);
+  hipLaunchKernelGGL(k_so_pack, dim3(g ? g : 1), dim3(256), 0, ctx->stream, k);
+  return hipGetLastError() == hipSuccess ? 0 : EMQX_GM_EDEVICE;
 }
 
 }  // namespace gm

@@ -486,7 +486,8 @@ class Context:
             lib().emqx_gm_csr_free(self.h, C.byref(d))
 
     def publish_window(self, index: Index, topics, exact: bool = True, shared=None, strategy="round_robin",
-                       hashes=None, seed: int = 0, dests=None, skip_node: Optional[int] = None):
+                       hashes=None, seed: int = 0, dests=None, skip_node: Optional[int] = None,
+                       subopts=None, msg_flags=None, msg_from=None, drop: bool = False):
         """A whole publish window in one call (emqx_gm_publish_window): the match
         and its fan-out as ``match_fanout``, the shared picks of ``shared`` (a
         SharedTable) as ``shared.pick`` on the matched rows with ``(strategy,
@@ -495,7 +496,14 @@ class Context:
         the speculation holds.  Returns ``(matches, deliveries, picks, plan,
         stats)``: ``picks`` is ``(row_off, members, slots)`` or None without
         ``shared``, ``plan`` a ForwardPlan or None without ``dests``, ``stats``
-        the call's emqx_gm_publish_stats as a dict."""
+        the call's emqx_gm_publish_stats as a dict.
+
+        With ``subopts`` (a SubOptTable bound to ``index``) the deliveries carry
+        their option bytes (emqx_gm_publish_window_deliver): the tuple's
+        ``deliveries`` is then the ``Delivered`` that ``subopts.deliver(matches,
+        msg_flags, msg_from, drop)`` returns, computed in the same round trip in
+        place of the plain fan-out, and ``stats`` gains ``deliveries_spec``,
+        ``n_deliveries``, ``n_dropped`` and ``cap_deliveries``."""
         from .cluster import _plan_to_numpy, _skip
         from .shared import _strategy
         tb, to = topics if isinstance(topics, tuple) else pack(topics)
@@ -514,8 +522,24 @@ class Context:
         o.dests = dests.h if dests is not None else None
         o.skip_node = _skip(skip_node)
         res, st = _lib.PublishResult(), _lib.PublishStats()
-        check(lib().emqx_gm_publish_window(self.h, index.h, _ptr(tb), _ptr(to), n, C.byref(o), C.byref(res),
-                                           C.byref(st)), self.h, "publish_window")
+        dl = dst = None
+        if subopts is None:
+            check(lib().emqx_gm_publish_window(self.h, index.h, _ptr(tb), _ptr(to), n, C.byref(o), C.byref(res),
+                                               C.byref(st)), self.h, "publish_window")
+        else:
+            from .subopts import _msg_args, _to_numpy
+            subopts._check_bound(index)
+            mf, fr = _msg_args(n, msg_flags, msg_from)
+            do = _lib.PublishDeliverOpts()
+            do.subopts = subopts.h
+            do.msg_flags = mf.ctypes.data
+            do.msg_from = fr.ctypes.data
+            do.mode = _lib.SO_DROP if drop else _lib.SO_FLAG
+            dl, dst = _lib.Deliveries(), _lib.PublishDeliverStats()
+            check(lib().emqx_gm_publish_window_deliver(self.h, index.h, _ptr(tb), _ptr(to), n, C.byref(o),
+                                                       C.byref(do), C.byref(res), C.byref(dl), C.byref(dst)),
+                  self.h, "publish_window_deliver")
+            st = dst.window
         try:
             picks = plan = None
             if shared is not None:
@@ -526,9 +550,15 @@ class Context:
             if dests is not None:
                 plan = _plan_to_numpy(res.forwards)
             stats = {name: int(getattr(st, name)) for name, _ in _lib.PublishStats._fields_}
-            return _csr_to_numpy(res.matches), _csr_to_numpy(res.deliveries), picks, plan, stats
+            if dl is None:
+                return _csr_to_numpy(res.matches), _csr_to_numpy(res.deliveries), picks, plan, stats
+            for name in ("deliveries_spec", "n_deliveries", "n_dropped", "cap_deliveries"):
+                stats[name] = int(getattr(dst, name))
+            return _csr_to_numpy(res.matches), _to_numpy(dl, drop), picks, plan, stats
         finally:
             lib().emqx_gm_publish_result_free(self.h, C.byref(res))
+            if dl is not None:
+                lib().emqx_gm_deliveries_free(self.h, C.byref(dl))
 
     def publish_windows(self, index: Index, windows, hashes=None, exact: bool = True, shared=None,
                         strategy="round_robin", seed: int = 0, dests=None, skip_node: Optional[int] = None,

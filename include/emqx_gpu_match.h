@@ -68,8 +68,9 @@
  *   host path:          GM_HOST_SIMPLE, GM_HOST_PIPE, GM_HOST_CHUNK,
  *     GM_HOST_THREADS, GM_HOST_BOUNCE, GM_HOST_WIDE_ROWS, GM_HOST_OFF32,
  *     GM_FANOUT_MULTI_MIN, GM_FANOUT_SIMPLE, GM_FANOUT_FUSED_ONLY;
- *   publish window:     GM_PW_CAP_HITS, GM_PW_CAP_PAIRS (the speculative pick /
- *     plan capacities as given; 0: that part is not speculated);
+ *   publish window:     GM_PW_CAP_HITS, GM_PW_CAP_PAIRS, GM_PW_CAP_DELIVERIES
+ *     (the speculative pick / plan / deliveries capacities as given; 0: that
+ *     part is not speculated);
  *   updates:            GM_UPDATE_OVERLAY, GM_UPDATE_UNFUSED, GM_SPARE_BLOB_MIN;
  *   diagnostics:        GM_UPDATE_TIMING, GM_INDEX_STATS, GM_INDEX_VERIFY.
  */
@@ -950,6 +951,52 @@ int emqx_gm_publish_window(emqx_gm_ctx *ctx, const emqx_gm_index *idx, const uin
                            emqx_gm_publish_result *out, emqx_gm_publish_stats *stats /* may be NULL */);
 /* frees every member of a result and zeroes it */
 int emqx_gm_publish_result_free(emqx_gm_ctx *ctx, emqx_gm_publish_result *res);
+
+/* ---- a publish window whose deliveries carry their option bytes ----
+ * A window's local deliveries are not finished until each one has its
+ * delivery byte (emqx_gm_deliver above).  emqx_gm_publish_window_deliver queues
+ * that work as a THIRD speculative part behind the window's rows, beside the
+ * picks and the plan and in place of the plain fan-out (in EMQX_GM_SO_FLAG mode
+ * the ids are the fan-out's), so the window still needs one wait in total.
+ * CONTRACT: on the same tables the result is bit-equal to
+ *   emqx_gm_publish_window(opts) followed by emqx_gm_deliver(subopts,
+ *   &out->matches, msg_flags, msg_from, mode):
+ * out->matches, pick_members, pick_slots, forwards and the shared table's
+ * state afterwards are the window call's; out->deliveries is zeroed; `deliv` is
+ * the deliver call's, array for array (deliveries.row_off, deliveries.ids,
+ * dopt, row_dropped -- NULL in FLAG mode -- and n_dropped).  deliv's arrays are
+ * host pointers from the context's host pool: free them with
+ * emqx_gm_deliveries_free.
+ * SPECULATION: the deliveries run into the fan-out's own capacity (this
+ * context's recent deliveries per match; GM_PW_CAP_DELIVERIES gives it as it
+ * is, 0: not speculated).  They hold if the rows were the speculative ones and
+ * the (post-drop) total fits; else they run again at exact size on the rows
+ * still in HBM, before the picks are committed.
+ * A window emqx_gm_publish_window would not serve in one round trip takes
+ * emqx_gm_match, the pick, the plan and emqx_gm_deliver in sequence
+ * (device_waits is then 0: not counted).
+ * ERRORS: every refusal of emqx_gm_publish_window; a NULL dopts, deliv or
+ * subopts, NULL msg_flags / msg_from with n_topics > 0, an unknown mode, a
+ * msg_flags byte with bits 4-7 set or QoS 3, a table on another device or bound
+ * to a snapshot other than idx: EMQX_GM_EINVAL (a host-only table:
+ * EMQX_GM_EUNSUPPORTED) -- all before any device work, no output touched, no
+ * state changed.  On any later error every output is zeroed, nothing is held
+ * and the shared state is unchanged. */
+typedef struct {
+  emqx_gm_subopts *subopts;  /* required; bound to idx, on the window's device        */
+  const uint8_t *msg_flags;  /* host, n_topics entries, as emqx_gm_deliver             */
+  const uint32_t *msg_from;  /* host, n_topics entries (EMQX_GM_SO_NO_PUBLISHER: none) */
+  uint32_t mode;             /* EMQX_GM_SO_FLAG / EMQX_GM_SO_DROP                      */
+} emqx_gm_publish_deliver_opts;
+typedef struct {
+  emqx_gm_publish_stats window;  /* fanout_spec stays 0: no plain fan-out is made */
+  uint8_t deliveries_spec;       /* 1: the deliveries came from the first round trip */
+  uint64_t n_deliveries, n_dropped, cap_deliveries; /* cap 0: not speculated */
+} emqx_gm_publish_deliver_stats;
+int emqx_gm_publish_window_deliver(emqx_gm_ctx *ctx, const emqx_gm_index *idx, const uint8_t *topic_bytes,
+                                   const uint64_t *topic_off, uint64_t n_topics, const emqx_gm_publish_opts *opts,
+                                   const emqx_gm_publish_deliver_opts *dopts, emqx_gm_publish_result *out,
+                                   emqx_gm_deliveries *deliv, emqx_gm_publish_deliver_stats *stats /* may be NULL */);
 
 /* ---- whole publish windows coalesced into one device round trip (gm_publish.hip) ----
  * Every scheduler of a node runs emqx_broker:publish/1 -> route/2 per message

@@ -16,6 +16,7 @@
 -export([load_shared/3, load_shared/4, pick_shared/4, pick_shared_nif/5]).
 -export([publish_window/4, publish_window_nif/5]).
 -export([load_subopts/3, deliver/5]).
+-export([publish_window_deliver/7, publish_window_deliver_nif/9]).
 -export([load_authz/1, authorize_batch/2, authz_rule/2, authz_request/3, authorize/5]).
 -export([match/2]).
 
@@ -205,6 +206,33 @@ publish_window(Table, Msgs, Strategy, Seed) ->
           [{[{binary(), [non_neg_integer()]}], [{binary(), {non_neg_integer(), non_neg_integer()}}]}] |
           {error, term()}.
 publish_window_nif(_Table, _Topics, _Strategy, _Hashes, _Seed) -> erlang:nif_error(nif_not_loaded).
+
+%% A publish window whose local deliveries carry their option bytes
+%% (emqx_gm_publish_window_deliver): per message {Topic, ClientId}, in order,
+%% {what deliver/5 gives for the topic, what pick_shared/4 gives for it}, the
+%% deliveries with their bytes computed in the window's one device round trip in
+%% place of the plain fan-out.  Shared and SubOpts must be tables of the same
+%% snapshot (load_index/2); MsgFlags, From and Mode as deliver/5 takes them.
+-spec publish_window_deliver(reference(), reference(), [{binary(), term()}], atom(), non_neg_integer(),
+                             {[0..15], [non_neg_integer()]}, 0 | 1) ->
+          [{{[{non_neg_integer(), 0..31}], non_neg_integer()},
+            [{binary(), {non_neg_integer(), non_neg_integer()}}]}] | {error, term()}.
+publish_window_deliver(Shared, SubOpts, Msgs, Strategy, Seed, {MsgFlags, From}, Mode) ->
+    Topics = [T || {T, _} <- Msgs],
+    {S, Hashes} = case Strategy of
+                      hash_topic -> {0, [erlang:phash2(T) || {T, _} <- Msgs]};
+                      H when H =:= hash; H =:= hash_clientid -> {0, [erlang:phash2(C) || {_, C} <- Msgs]};
+                      round_robin -> {1, []};
+                      sticky -> {2, []};
+                      random -> {3, []}
+                  end,
+    publish_window_deliver_nif(Shared, SubOpts, Topics, S, Hashes, Seed band 16#FFFFFFFF, MsgFlags, From, Mode).
+
+-spec publish_window_deliver_nif(reference(), reference(), [binary()], 0..3, [non_neg_integer()], non_neg_integer(),
+                                 [0..15], [non_neg_integer()], 0 | 1) ->
+          [{{[{non_neg_integer(), 0..31}], non_neg_integer()},
+            [{binary(), {non_neg_integer(), non_neg_integer()}}]}] | {error, term()}.
+publish_window_deliver_nif(_Sh, _So, _Topics, _Strategy, _Hashes, _Seed, _Flags, _From, _Mode) -> erlang:nif_error(nif_not_loaded).
 
 %% The authorization chain (file and built-in-database sources, in order) as
 %% one table in HBM (emqx_gm_authz_build).  Segment = {Kind, [{Key, [Rule]}]}:

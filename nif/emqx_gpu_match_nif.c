@@ -1271,6 +1271,107 @@ static ERL_NIF_TERM deliver_nif(ErlNifEnv *env, int argc, const ERL_NIF_TERM arg
   return result;
 }
 
+/* publish_window_deliver_nif(Shared, SubOpts, [Topic], Strategy :: 0..3, [Hash], Seed, [MsgFlags], [From],
+ *                            Mode :: 0 | 1) -> [{{[{SubId, Byte}], Dropped}, [{Filter, {GroupId, MemberId}}]}]
+ * per topic, in batch order: what deliver/5 gives for it and what pick_shared_nif/5
+ * gives for it, from ONE emqx_gm_publish_window_deliver -- the deliveries with
+ * their option bytes run as a third part of the window's one device round trip,
+ * in place of the plain fan-out.  Both tables must be bound to the same snapshot
+ * (from load_index/2); the library refuses another pairing. */
+static ERL_NIF_TERM publish_window_deliver_nif(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_shared_res *r;
+  gm_subopts_res *so;
+  uint8_t *tb, *mf;
+  uint64_t *to, n, i, k;
+  unsigned strategy, seed, nh = 0, nf = 0, nfr = 0, mode, v = 0;
+  uint32_t *hash, *from;
+  emqx_gm_publish_opts o;
+  emqx_gm_publish_deliver_opts dopts;
+  emqx_gm_publish_result w;
+  emqx_gm_deliveries d;
+  ERL_NIF_TERM result, *rows, h, t;
+  int rc, ok = 1, bad = 0;
+  (void)argc;
+  if (!enif_get_resource(env, argv[0], SHARED_RT, (void **)&r) ||
+      !enif_get_resource(env, argv[1], SUBOPTS_RT, (void **)&so) || !enif_get_uint(env, argv[3], &strategy) ||
+      !enif_get_list_length(env, argv[4], &nh) || !enif_get_uint(env, argv[5], &seed) ||
+      !enif_get_list_length(env, argv[6], &nf) || !enif_get_list_length(env, argv[7], &nfr) ||
+      !enif_get_uint(env, argv[8], &mode))
+    return enif_make_badarg(env);
+  if (!pack_topics(env, argv[2], &tb, &to, &n)) return enif_make_badarg(env);
+  if (nf != n || nfr != n || (strategy == EMQX_GM_SHARE_HASH && nh != n)) {
+    free_topics(tb, to);
+    return enif_make_badarg(env);
+  }
+  hash = enif_alloc(sizeof(uint32_t) * (n ? n : 1));
+  mf = enif_alloc(n ? n : 1);
+  from = enif_alloc(sizeof(uint32_t) * (n ? n : 1));
+  if (strategy == EMQX_GM_SHARE_HASH)
+    for (i = 0, t = argv[4]; ok && enif_get_list_cell(env, t, &h, &t); ++i) {
+      ok = enif_get_uint(env, h, &v);
+      if (ok) hash[i] = v;
+    }
+  for (i = 0, t = argv[6]; ok && enif_get_list_cell(env, t, &h, &t); ++i) {
+    ok = enif_get_uint(env, h, &v) && v <= 255; /* (bits 4-7 and QoS 3: refused by the library) */
+    if (ok) mf[i] = (uint8_t)v;
+  }
+  for (i = 0, t = argv[7]; ok && enif_get_list_cell(env, t, &h, &t); ++i) {
+    ok = enif_get_uint(env, h, &v);
+    if (ok) from[i] = v;
+  }
+  rc = EMQX_GM_OK;
+  if (ok) {
+    memset(&o, 0, sizeof(o));
+    o.flags = EMQX_GM_WITH_EXACT;
+    o.shared = r->sh;
+    o.strategy = strategy;
+    o.seed = seed;
+    o.msg_hash = strategy == EMQX_GM_SHARE_HASH ? hash : NULL;
+    memset(&dopts, 0, sizeof(dopts));
+    dopts.subopts = so->so;
+    dopts.msg_flags = mf;
+    dopts.msg_from = from;
+    dopts.mode = mode;
+    rc = emqx_gm_publish_window_deliver(CTX, r->idx, tb, to, n, &o, &dopts, &w, &d, NULL);
+  }
+  free_topics(tb, to);
+  enif_free(hash);
+  enif_free(mf);
+  enif_free(from);
+  if (!ok) return enif_make_badarg(env);
+  if (rc != EMQX_GM_OK) return error_tuple(env, rc);
+  rows = enif_alloc(sizeof(ERL_NIF_TERM) * (n ? n : 1));
+  for (i = 0; i < n && !bad; ++i) {
+    ERL_NIF_TERM row = enif_make_list(env, 0), picks = enif_make_list(env, 0);
+    for (k = d.deliveries.row_off[i + 1]; k > d.deliveries.row_off[i]; --k)
+      row = enif_make_list_cell(
+          env, enif_make_tuple2(env, enif_make_uint(env, d.deliveries.ids[k - 1]), enif_make_uint(env, d.dopt[k - 1])),
+          row);
+    for (k = w.pick_members.row_off[i + 1]; k > w.pick_members.row_off[i] && !bad; --k) {
+      const uint8_t *p = NULL;
+      uint64_t l = 0;
+      uint32_t f = 0, g = 0;
+      if (emqx_gm_shared_slot(r->sh, w.pick_slots.ids[k - 1], &f, &g, NULL, NULL) != EMQX_GM_OK ||
+          emqx_gm_index_filter(r->idx, f, &p, &l) != EMQX_GM_OK) {
+        bad = 1;
+        break;
+      }
+      picks = enif_make_list_cell(
+          env,
+          enif_make_tuple2(env, enif_make_resource_binary(env, r, p, l),
+                           enif_make_tuple2(env, enif_make_uint(env, g), enif_make_uint(env, w.pick_members.ids[k - 1]))),
+          picks);
+    }
+    rows[i] = enif_make_tuple2(
+        env, enif_make_tuple2(env, row, enif_make_uint(env, d.row_dropped ? d.row_dropped[i] : 0)), picks);
+  }
+  result = bad ? error_tuple(env, EMQX_GM_EINVAL) : enif_make_list_from_array(env, rows, (unsigned)n);
+  enif_free(rows);
+  emqx_gm_publish_result_free(CTX, &w);
+  emqx_gm_deliveries_free(CTX, &d);
+  return result;
+}
+
 static ErlNifFunc funcs[] = {
     {"load_index", 1, load_index, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"load_index", 2, load_index, ERL_NIF_DIRTY_JOB_CPU_BOUND},
@@ -1294,6 +1395,7 @@ static ErlNifFunc funcs[] = {
     {"publish_window_nif", 5, publish_window_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"load_subopts", 3, load_subopts, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"deliver", 5, deliver_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"publish_window_deliver_nif", 9, publish_window_deliver_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"load_authz", 1, load_authz, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"authorize_batch", 2, authorize_batch, ERL_NIF_DIRTY_JOB_CPU_BOUND},
 };
