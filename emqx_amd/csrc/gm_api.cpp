@@ -416,16 +416,10 @@ int emqx_gm_close(emqx_gm_ctx* ctx) {
     for (auto& e : ctx->ev)
       if (e) hipEventDestroy(e);
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
-    if (ctx->stream2) {
-      hipStreamSynchronize(ctx->stream2);
-      hipStreamDestroy(ctx->stream2);
-    }
     if (ctx->stream_asm) {
       hipStreamSynchronize(ctx->stream_asm);
       hipStreamDestroy(ctx->stream_asm);
     }
-    for (auto& e : ctx->ov_ev)
-      if (e) hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_free) hipEventDestroy(e);
     for (void* p : ctx->pin_all) hipHostFree(p);
     if (ctx->ctr_ring) hipFree(ctx->ctr_ring);

@@ -178,12 +178,10 @@ struct emqx_gm_ctx {
   gm::HostPipe* host = nullptr;
   hipStream_t stream = nullptr;
   bool own_stream = false;
-  hipStream_t stream2 = nullptr;  // tokenizer stream of the overlapped match (GM_OVERLAP)
   // assembly stream (gm_match.hip MatchCall): a large device-buffer call's
   // scan + assembly run here behind its main pass, so the next call's main
   // pass (context stream) overlaps them
   hipStream_t stream_asm = nullptr;
-  hipEvent_t ov_ev[9] = {};
   std::recursive_mutex mu;
   gm::DevPool* pool = nullptr;
   gm::HostPool* hpool = nullptr;

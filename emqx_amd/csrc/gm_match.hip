@@ -7,7 +7,7 @@
 // Hot path (replaces emqx_trie:match/1 + emqx_router:match_routes/1,
 // apps/emqx/src/emqx_trie.erl:147-333, apps/emqx/src/emqx_router.erl:128-145):
 //
-//   k_match_fused  main pass (default): a block stages its 256 topics' text in
+//   k_match_fused  main pass: a block stages its 256 topics' text in
 //                  LDS; each lane splits its topic into words, hashes them and
 //                  resolves them in the word dictionary (verified
 //                  byte-for-byte) into registers; then each wave walks its
@@ -16,16 +16,12 @@
 //                  lane per round: an exact probe and a '+' probe per entry,
 //                  each one 16-B raw buffer load of a 32-B hot slot (edge probe
 //                  and node record in one line).  Matches are staged per tile
-//                  as [slot][lane].
-//   k_tokenize + k_walk_coop / k_walk
-//                  the same work as two kernels through HBM word ids (A/B
-//                  forms, GM_MATCH_MAIN; k_walk keeps a lane-private frontier
-//                  in registers).
-//   k_match_lds    the same walk with the frontier in LDS (capacity FC).  As
-//                  the LISTED pass it re-walks the topics whose frontier or
-//                  row outgrew the main pass (count read on the device, so no
+//                  as one compact list (or as [slot][lane] columns).
+//   k_match_lds    the listed pass: a lane-private walk with the frontier in
+//                  LDS (capacity FC) over the topics whose frontier or row
+//                  outgrew the main pass (count read on the device, so no
 //                  host round trip between the passes).
-//   (k_walk tile sums) / scan / k_assemble
+//   tile sums / scan / k_assemble, k_assemble_c
 //                  count -> scan -> write: builds the CSR (row_off u64, ids u32).
 //   k_slow_walk / k_slow_emit / k_copy_slow
 //                  device slow path: one workgroup per topic the listed pass
@@ -34,6 +30,14 @@
 //                  ascending id order.  No truncation, no CPU fallback.
 //   k_d0_refresh   the walk's level-0 record (IndexView::d0_root), rewritten
 //                  at build and after each in-place update (refresh_d0).
+//
+//   k_tokenize + k_walk
+//                  the main pass as two kernels through HBM word ids, k_walk
+//                  with a lane-private frontier in registers (A/B forms,
+//                  GM_MATCH_MAIN=split|splitw8).
+// The wave-cooperative walk as a kernel of its own behind k_tokenize
+// (k_walk_coop) and the two-stream tokenize/walk overlap (GM_OVERLAP) are gone;
+// DESIGN.md section 4 keeps their measurements against the fused kernel.
 //
 // Everything here is integer/byte work bound by HBM/L2 latency and bandwidth;
 // there is no MFMA.
@@ -110,8 +114,7 @@ struct WordTok {
 };
 
 // Tokenize the word starting at `pos`; leaves `pos` on the '/' (or end).
-template <class RD>
-__device__ __forceinline__ WordTok next_word(RD& rd, uint64_t& pos, uint64_t end) {
+__device__ __forceinline__ WordTok next_word(ByteReader& rd, uint64_t& pos, uint64_t end) {
   WordTok w;
   w.start = pos;
   w.head = 0;
@@ -241,8 +244,8 @@ struct HotRec {
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t hot_rsrc(const HotSlot* tab) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<HotSlot*>(tab), (short)0, 0x7FFFFFFF, 0x00020000);
 }
-// One table (or one level's part of it) as k_match_fused and k_walk_coop read
-// it.  FLAT false: through a buffer resource of the table's real byte size,
+// One table (or one level's part of it) as k_match_fused reads it.  FLAT
+// false: through a buffer resource of the table's real byte size,
 // built from wave-uniform values only (kernel arguments, a readfirstlane'd
 // level), with 32-bit per-lane byte offsets -- no 64-bit address arithmetic per
 // lane, and the hardware range check drops the request of a lane that passes
@@ -396,9 +399,10 @@ __device__ __forceinline__ void stage_st(uint32_t* base, uint32_t k, uint32_t v,
   }
 }
 
+// ---- the row, visit and probe steps of the lane-private walks (k_match_lds, k_walk) ----
 // Per-lane match staging: emit one filter id into the topic's row (slot m_n
-// of the topic's lane column in its tile; srow = &stage[stage_index(tile, 0,
-// lane)]).
+// of the topic's lane column in its tile, srow = &stage[stage_index(tile, 0,
+// lane)]; or of its listed row).
 #define GM_EMIT(f)                                \
   do {                                            \
     if (m_n < MC) srow[m_n * sstr] = (f);         \
@@ -409,7 +413,7 @@ __device__ __forceinline__ void stage_st(uint32_t* base, uint32_t k, uint32_t v,
 // 'match_#' for it; on the topic's last word also its own filter
 // (lookup_topic/3: only wildcard filters in trie mode; the '$X' quirk of
 // emqx_trie.erl:275-276 for single-word '$' topics); otherwise push it onto
-// the next frontier (GM_PUSH is defined per kernel).
+// the next frontier (GM_PUSH, below).
 #define GM_VISIT(hs, r)                                                                 \
   do {                                                                                  \
     if (((r).a.w & HF_MASK) != HF_NONE) GM_EMIT((r).a.w & HF_MASK);                     \
@@ -438,11 +442,10 @@ __device__ __forceinline__ void stage_st(uint32_t* base, uint32_t k, uint32_t v,
     }                                                        \
   } while (0)
 
-// ---- probes shared by the walk kernels -------------------------------------
-// Frontier (k_walk): at most RFC entries {hot id | FR_PLUS, exact-child
+// Frontier of k_walk: at most RFC entries {hot id | FR_PLUS, exact-child
 // signature} in registers (pushes are select chains over static indices, so
 // nothing spills to scratch).  A lane whose frontier outgrows RFC, or whose row
-// outgrows FAST_MC, is queued for the listed LDS pass and contributes nothing
+// outgrows FAST_MC, is queued for the listed pass and contributes nothing
 // in the main pass.
 constexpr int RFC = 4;
 
@@ -493,11 +496,11 @@ __device__ __forceinline__ bool plus_is_inline(uint32_t lvl, uint32_t id) { retu
     }                                                                                                     \
   } while (0)
 
-// ---- k_match_lds ----------------------------------------------------------
-// Frontier entries double buffered in LDS, FC per lane.  LISTED: grid-stride
-// over the topics list_in[0 .. *list_n) (the main pass's overflow queue; the
-// count is read on the device); otherwise one topic per thread.  Overflow
-// here (frontier > FC or row > FAST_MC) is queued for k_slow_walk.
+// ---- k_match_lds: the listed pass -------------------------------------------
+// Grid-stride over the topics list_in[0 .. *list_n) (the main pass's overflow
+// queue; the count is read on the device), a topic per lane, its frontier
+// entries double buffered in LDS, FC per lane.  Overflow here (frontier > FC or
+// row > FAST_MC) is queued for k_slow_walk.
 #define GM_PUSH(idv, sigv)                                                 \
   do {                                                                     \
     if (nn < FC) s_fr[nb][nn][threadIdx.x] = make_uint2((idv), (sigv));    \
@@ -507,28 +510,31 @@ __device__ __forceinline__ bool plus_is_inline(uint32_t lvl, uint32_t id) { retu
 // CMP (the main pass staged compactly): the listed rows go to their own
 // buffer, row `item` of lstage (FAST_MC ids, stride 1), their length to
 // lcnt[item] and cnt[t] = LIST_BIT | item; items past lcap go to the slow path.
-template <bool EXACT, int FC, bool LISTED, bool CMP = false>
+// (The topic count and the wildcard counter, the main pass's, are not read
+// here -- the main pass has counted a listed wildcard topic, one deeper than
+// TOK_LMAX; both keep their places in the argument list.)
+template <bool EXACT, int FC, bool CMP>
 __global__ __launch_bounds__(256) void k_match_lds(const uint8_t* __restrict__ tb,
-                                                   const uint64_t* __restrict__ toff, uint64_t n, IndexView ix,
+                                                   const uint64_t* __restrict__ toff, uint64_t /*n*/, IndexView ix,
                                                    uint32_t* __restrict__ cnt, uint32_t* __restrict__ stage,
                                                    const uint32_t* __restrict__ list_in,
                                                    const uint32_t* __restrict__ list_n,
                                                    uint32_t* __restrict__ ovf_list, uint32_t* __restrict__ ovf_n,
                                                    unsigned long long* __restrict__ probe_ctr,
-                                                   unsigned long long* __restrict__ wild_ctr,
-                                                   uint64_t* __restrict__ tsum, uint32_t* __restrict__ lstage = nullptr,
-                                                   uint32_t* __restrict__ lcnt = nullptr, uint64_t lcap = 0) {
+                                                   unsigned long long* __restrict__ /*wild_ctr*/,
+                                                   uint64_t* __restrict__ tsum, uint32_t* __restrict__ lstage,
+                                                   uint32_t* __restrict__ lcnt, uint64_t lcap) {
   constexpr int MC = FAST_MC;
   constexpr uint32_t sstr = CMP ? 1u : 64u;
   // frontier entry: {hot id | FR_PLUS, exact-child signature}, double buffered
   __shared__ uint2 s_fr[2][FC][256];
   const int tid = threadIdx.x, lane = tid & 63;
-  const uint64_t n_items = LISTED ? uint64_t(*list_n) : n;
-  uint32_t probes = 0, wilds = 0;
+  const uint64_t n_items = *list_n;
+  uint32_t probes = 0;
 
   for (uint64_t item = uint64_t(blockIdx.x) * 256u + tid; item < n_items;
        item += uint64_t(gridDim.x) * 256u) {
-    const uint64_t t = LISTED ? uint64_t(list_in[item]) : item;
+    const uint64_t t = list_in[item];
     const uint64_t tile = t >> 6;
     if (CMP && item >= lcap) {  // no listed row left: the slow path
       cnt[t] = OVF_BIT;
@@ -615,55 +621,27 @@ __global__ __launch_bounds__(256) void k_match_lds(const uint8_t* __restrict__ t
       cnt[t] = ovf ? OVF_BIT : m_n;
     }
     if (ovf) ovf_list[atomicAdd(ovf_n, 1u)] = uint32_t(t);
-    else if (LISTED) atomicAdd(reinterpret_cast<unsigned long long*>(tsum + tile), (unsigned long long)m_n);
+    else atomicAdd(reinterpret_cast<unsigned long long*>(tsum + tile), (unsigned long long)m_n);
     probes += tprobes;
-    // (a listed wildcard topic -- one deeper than TOK_LMAX -- is already in wild_ctr: the main pass counted it)
-    wilds += !LISTED && wild ? 1u : 0u;
-    if (!LISTED) break;
   }
-  // per-wave counters (one atomic per wave)
-  uint32_t ptot, wtot;
+  // the wave's probes (one atomic per wave; an idle listed grid adds nothing:
+  // 2,048 same-address atomics cost ~20 us)
+  uint32_t ptot;
   wave_excl_scan(probes, ptot);
-  wave_excl_scan(wilds, wtot);
-  if (lane == 0) {
-    if (LISTED) {
-      if (ptot) atomicAdd(probe_ctr, (unsigned long long)ptot);  // (an idle listed grid adds nothing: 2,048
-    }                                                             //  same-address atomics cost ~20 us)
-    else if (((uint64_t(blockIdx.x) * 256u + tid) >> 6) * 64 < n)
-      probe_ctr[(uint64_t(blockIdx.x) * 256u + tid) >> 6] = ptot;  // per-tile slot, see k_match_reg
-    if (wtot) atomicAdd(wild_ctr, (unsigned long long)wtot);
-  }
+  if (lane == 0 && ptot) atomicAdd(probe_ctr, (unsigned long long)ptot);
 }
 #undef GM_PUSH
 
-// ---- split form: k_tokenize + k_walk --------------------------------------
-// The per-topic front end (byte scan, word hash, dictionary lookup) and the
-// trie walk have different shapes: the first is streaming ALU work over the
-// topic bytes, the second a chain of dependent gathers.  Split, each kernel
-// keeps only its own state live, so the walk runs at full occupancy.
-//
-// k_tokenize writes, per topic, hdr = levels | TOK_DOLLAR | TOK_WILD | TOK_DEEP
-// and the word id of each level (NONE for a word no filter uses) into
-// wids[level][topic] (level < TOK_LMAX), a layout the walk reads coalesced.
+// ---- the tokenizer ------------------------------------------------------------
+// Per topic: a header = levels | TOK_DOLLAR | TOK_WILD | TOK_DEEP, and the word
+// id of each level below TOK_LMAX (NONE for a word no filter uses), handed to a
+// sink level by level; k_match_fused keeps them in registers (WidsToRegs),
+// k_tokenize writes them to HBM (WidsToHbm).
 constexpr int TOK_LMAX = 8;
+// k_match_fused: levels scanned, and dictionary slots in flight, at a time
+// (tokenize_grouped; k_tokenize's: GM_TOK_GROUP)
+constexpr int TOK_GROUP = 3;
 constexpr uint32_t TOK_DOLLAR = 1u << 8, TOK_WILD = 1u << 9, TOK_DEEP = 1u << 10;
-
-// Reader over topic text staged in LDS (8-byte words; `lo` = the absolute
-// batch offset of lds[0]), with the same one-word cache as ByteReader.
-struct LdsReader {
-  const uint64_t* lds;
-  uint64_t lo;
-  uint64_t cached_addr;
-  uint64_t cached;
-  __device__ __forceinline__ uint32_t get(uint64_t p) {
-    const uint64_t a = p & ~7ull;
-    if (a != cached_addr) {
-      cached_addr = a;
-      cached = lds[(a - lo) >> 3];
-    }
-    return uint32_t(cached >> ((p & 7) * 8)) & 0xFFu;
-  }
-};
 
 // Word scan over LDS-staged text, 8 bytes per step (SWAR): the next '/' is the
 // lowest zero byte of (word ^ 0x2F..2F) at or after the start (an exact
@@ -677,51 +655,13 @@ __device__ __forceinline__ uint64_t funnel8(const uint64_t* lds, uint64_t wi, ui
   return sh ? (a >> sh) | (lds[wi + 1] << (64 - sh)) : a;
 }
 
-__device__ __forceinline__ WordTok next_word(LdsReader& rd, uint64_t& pos, uint64_t end) {
-  constexpr uint64_t SL = 0x2F2F2F2F2F2F2F2Full, M7 = 0x7F7F7F7F7F7F7F7Full;
-  // exact per-byte zero test (no borrow between bytes): bit 7 of a byte of
-  // zbytes(y) is set iff that byte of y is 0
-  auto zbytes = [](uint64_t y) { return ~(((y & M7) + M7) | y | M7); };
-  WordTok w;
-  w.start = pos;
-  const uint64_t rel = pos - rd.lo;
-  const uint64_t w0 = rel >> 3;
-  const uint32_t sh = uint32_t(rel & 7) * 8;
-  // find the end of the word
-  uint64_t wi = w0, e = end;
-  uint64_t z = zbytes(rd.lds[wi] ^ SL) & (~0ull << sh);  // bytes before pos do not count
-  for (;;) {
-    if (z) {
-      const uint64_t at = rd.lo + wi * 8 + (__builtin_ctzll(z) >> 3);
-      e = at < end ? at : end;
-      break;
-    }
-    if (rd.lo + (wi + 1) * 8 >= end) break;
-    ++wi;
-    z = zbytes(rd.lds[wi] ^ SL);
-  }
-  const uint32_t len = uint32_t(e - pos);
-  uint32_t h = DICT_HASH_SEED;
-  uint64_t head = 0;
-  for (uint32_t k = 0; k < len; k += 8) {
-    uint64_t c = funnel8(rd.lds, w0 + (k >> 3), sh);
-    if (len - k < 8) c &= (1ull << ((len - k) * 8)) - 1;
-    if (k == 0) head = c;
-    h = dict_hash_step(h, c);
-  }
-  w.h = dict_hash_final(h, len);
-  w.head = head;
-  w.len = len;
-  w.b0 = uint32_t(head & 0xFF);
-  pos = e;
-  return w;
-}
-
-// The same scan in 32-bit offsets relative to the block's staged text (at
-// most TOK_STAGE bytes): no 64-bit position arithmetic in the byte scan.
+// The scan, in 32-bit offsets relative to the block's staged text (at most
+// TOK_STAGE bytes): no 64-bit position arithmetic in the byte scan.
 // `w.start` is relative too, so the word's tail is read from `tb + lo`.
 __device__ __forceinline__ WordTok next_word_s(const uint64_t* lds, uint32_t& pos, uint32_t end) {
   constexpr uint64_t SL = 0x2F2F2F2F2F2F2F2Full, M7 = 0x7F7F7F7F7F7F7F7Full;
+  // exact per-byte zero test (no borrow between bytes): bit 7 of a byte of
+  // zbytes(y) is set iff that byte of y is 0
   auto zbytes = [](uint64_t y) { return ~(((y & M7) + M7) | y | M7); };
   WordTok w;
   w.start = pos;
@@ -768,7 +708,7 @@ __device__ __forceinline__ WordTok next_word_s(const uint64_t* lds, uint32_t& po
   return w;
 }
 
-// Staged-text form of tokenize_topic: relative 32-bit positions, and the
+// Staged-text form of tokenize_topic (k_tokenize<1>): relative 32-bit positions, and the
 // level's wids[] slot advanced by n (no lev * n product per level).
 __device__ __forceinline__ uint32_t tokenize_staged(const uint64_t* lds, uint32_t pos, uint32_t end,
                                                     const IndexView& ix, const uint8_t* tb_lo, uint64_t n,
@@ -803,15 +743,9 @@ __device__ __forceinline__ uint32_t tokenize_staged(const uint64_t* lds, uint32_
   return (lev < 255u ? lev : 255u) | fl;
 }
 
-// Grouped form: the words of G levels are scanned first and their first
-// dictionary slots loaded together, then resolved -- G L2 round trips in
-// flight per lane instead of the one-ahead prefetch above (the tokenizer
-// waits on the dictionary most of its time).  A word is kept as 4 VGPRs
-// (head, hash, start | len << 16; staged text is < 64 KiB) until it resolves.
-// Same hdr/wids as tokenize_topic: levels past TOK_LMAX are only counted
-// and checked for wildcards.
-// Where the word ids of one topic go: level-major HBM for k_walk / k_walk_coop,
-// registers for the fused kernel.  Called for levels 0, 1, 2, ... in order.
+// Where the word ids of one topic go: level-major HBM for k_walk (wids[level][topic],
+// a layout the walk reads coalesced), registers for the fused kernel.  Called for
+// levels 0, 1, 2, ... in order.
 template <bool NT>
 struct WidsToHbm {
   uint32_t* wp;  // wids + t
@@ -830,10 +764,16 @@ struct WidsToRegs {
   }
 };
 
-// DBUF (k_match_fused's buffer form): the words' first dictionary slots are
-// raw buffer loads (32-bit offsets from ix.dict) that every lane issues; a
-// lane without a word at that level passes an out-of-range offset.
-template <int G, bool DBUF = false, class SINK>
+// Staged text, grouped: the words of G levels are scanned first and their
+// first dictionary slots loaded together, then resolved -- G L2 round trips in
+// flight per lane instead of tokenize_topic's one-ahead prefetch (the
+// tokenizer waits on the dictionary most of its time).  A word is kept as 4
+// VGPRs (head, hash, start | len << 16; staged text is < 64 KiB) until it
+// resolves.  Levels past TOK_LMAX are only counted and checked for wildcards.
+// DBUF (the buffer form): the words' first dictionary slots are raw buffer
+// loads (32-bit offsets from ix.dict) that every lane issues; a lane without
+// a word at that level passes an out-of-range offset.
+template <int G, bool DBUF, class SINK>
 __device__ __forceinline__ uint32_t tokenize_grouped(const uint64_t* lds, uint32_t pos, uint32_t end,
                                                      const IndexView& ix, const uint8_t* tb_lo, SINK&& sink) {
   uint32_t lev = 0, fl = 0;
@@ -900,10 +840,11 @@ __device__ __forceinline__ uint32_t tokenize_grouped(const uint64_t* lds, uint32
   return (lev < 255u ? lev : 255u) | fl;
 }
 
-// One topic: words -> dictionary ids, the next word's first dictionary slot
-// loaded while this word resolves.
-template <class RD, class SINK>
-__device__ __forceinline__ uint32_t tokenize_topic(RD& rd, uint64_t pos, uint64_t end, const IndexView& ix,
+// Unstaged text (a block whose text does not fit TOK_STAGE): one topic from
+// global memory, the next word's first dictionary slot loaded while this word
+// resolves.
+template <class SINK>
+__device__ __forceinline__ uint32_t tokenize_topic(ByteReader& rd, uint64_t pos, uint64_t end, const IndexView& ix,
                                                    const uint8_t* tb, SINK&& sink) {
   uint32_t lev = 0, fl = 0;
   WordTok w = next_word(rd, pos, end);
@@ -938,6 +879,10 @@ __device__ __forceinline__ uint32_t tokenize_topic(RD& rd, uint64_t pos, uint64_
 // at every 8-byte boundary); a longer block reads global memory directly.
 constexpr int TOK_STAGE = 16384;
 
+// ---- split A/B forms (GM_MATCH_MAIN): k_tokenize + k_walk -------------------
+// The same work as two kernels: k_tokenize writes, per topic, its header and
+// the word id of each level below TOK_LMAX to HBM (hdr, wids[level][topic]);
+// k_walk reads them back.  DESIGN.md section 4 has their measurements.
 template <int G, bool NT>
 __global__ __launch_bounds__(256) void k_tokenize(const uint8_t* __restrict__ tb, const uint64_t* __restrict__ toff,
                                                   uint64_t n, IndexView ix, uint32_t* __restrict__ hdr,
@@ -960,7 +905,7 @@ __global__ __launch_bounds__(256) void k_tokenize(const uint8_t* __restrict__ tb
     if constexpr (G == 1)
       h = tokenize_staged(s_txt, uint32_t(pos - lo), uint32_t(end - lo), ix, tb + lo, n, wids + t);
     else
-      h = tokenize_grouped<G>(s_txt, uint32_t(pos - lo), uint32_t(end - lo), ix, tb + lo, WidsToHbm<NT>{wids + t, n});
+      h = tokenize_grouped<G, false>(s_txt, uint32_t(pos - lo), uint32_t(end - lo), ix, tb + lo, WidsToHbm<NT>{wids + t, n});
   } else {
     ByteReader rd{tb, ~0ull, 0};
     h = tokenize_topic(rd, pos, end, ix, tb, WidsToHbm<NT>{wids + t, n});
@@ -968,8 +913,8 @@ __global__ __launch_bounds__(256) void k_tokenize(const uint8_t* __restrict__ tb
   st_s<NT>(hdr + t, h);
 }
 
-// k_walk: the NFA walk over pre-resolved word ids, frontier in registers as
-// in k_match_reg.  Deep topics (more than TOK_LMAX levels) are queued for the
+// k_walk: the NFA walk over pre-resolved word ids, a lane-private frontier in
+// registers.  Deep topics (more than TOK_LMAX levels) are queued for the
 // listed pass, which tokenizes for itself.
 #define GM_PUSH(idv, sigv)                                \
   do {                                                    \
@@ -983,7 +928,7 @@ __global__ __launch_bounds__(256) void k_tokenize(const uint8_t* __restrict__ tb
     ++nn;                                                 \
   } while (0)
 
-template <bool EXACT, int MINW, bool PAIR>
+template <bool EXACT, int MINW>
 __global__ __launch_bounds__(256, MINW) void k_walk(const uint8_t* __restrict__ tb, const uint64_t* __restrict__ toff,
                                                     uint64_t n, IndexView ix, const uint32_t* __restrict__ hdr,
                                                     const uint32_t* __restrict__ wids, uint32_t* __restrict__ cnt,
@@ -1063,39 +1008,17 @@ __global__ __launch_bounds__(256, MINW) void k_walk(const uint8_t* __restrict__ 
           for (int q = 0; q < RFC; ++q)
             if ((fw[q] & fb[q]) != fb[q]) xmask &= ~(1u << q);
         }
-        if (PAIR) {
 #pragma unroll
-          for (int i = 0; i < RFC; i += 2) {
-            if (uint32_t(i) < cur_n) {
-              const bool hb = uint32_t(i + 1) < cur_n;
-              const uint32_t ia = fid[i] & ID_MASK, ib = fid[i + 1] & ID_MASK;
-              const bool ax = (xmask >> i) & 1u, ap = (fid[i] & FR_PLUS) != 0;
-              const bool bx = (xmask >> (i + 1)) & 1u, bp = hb && (fid[i + 1] & FR_PLUS) != 0;
-              uint32_t sax = 0, sap = 0, sbx = 0, sbp = 0;
-              HotRec rax{}, rap{}, rbx{}, rbp{};
-              GM_PROBE_ISSUE(ax, ia, false, sax, rax);
-              GM_PROBE_ISSUE(ap, ia, true, sap, rap);
-              GM_PROBE_ISSUE(bx, ib, false, sbx, rbx);
-              GM_PROBE_ISSUE(bp, ib, true, sbp, rbp);
-              GM_PROBE_TAKE(ax, ia, false, sax, rax);
-              GM_PROBE_TAKE(ap, ia, true, sap, rap);
-              GM_PROBE_TAKE(bx, ib, false, sbx, rbx);
-              GM_PROBE_TAKE(bp, ib, true, sbp, rbp);
-            }
-          }
-        } else {
-#pragma unroll
-          for (int i = 0; i < RFC; ++i) {
-            if (uint32_t(i) < cur_n) {
-              const uint32_t ia = fid[i] & ID_MASK;
-              const bool ax = (xmask >> i) & 1u, ap = (fid[i] & FR_PLUS) != 0;
-              uint32_t sax = 0, sap = 0;
-              HotRec rax{}, rap{};
-              GM_PROBE_ISSUE(ax, ia, false, sax, rax);
-              GM_PROBE_ISSUE(ap, ia, true, sap, rap);
-              GM_PROBE_TAKE(ax, ia, false, sax, rax);
-              GM_PROBE_TAKE(ap, ia, true, sap, rap);
-            }
+        for (int i = 0; i < RFC; ++i) {
+          if (uint32_t(i) < cur_n) {
+            const uint32_t ia = fid[i] & ID_MASK;
+            const bool ax = (xmask >> i) & 1u, ap = (fid[i] & FR_PLUS) != 0;
+            uint32_t sax = 0, sap = 0;
+            HotRec rax{}, rap{};
+            GM_PROBE_ISSUE(ax, ia, false, sax, rax);
+            GM_PROBE_ISSUE(ap, ia, true, sap, rap);
+            GM_PROBE_TAKE(ax, ia, false, sax, rax);
+            GM_PROBE_TAKE(ap, ia, true, sap, rap);
           }
         }
         if (nn > RFC) {
@@ -1143,20 +1066,17 @@ __global__ __launch_bounds__(256, MINW) void k_walk(const uint8_t* __restrict__ 
 #undef GM_WILD_ROW
 #undef GM_EMIT
 
-// ---- k_walk_coop: the wave's frontier as one compacted work list ---------
-// k_walk gives every lane its own topic's frontier, so at each level a wave
-// runs as many probe rounds as its LONGEST frontier (C2: ~1.6 entries per
-// topic on average, but the longest of 64 lanes is 3-4) and pays the exec-mask
+// ---- the coop walk: the wave's frontier as one compacted work list ---------
+// A lane-private frontier per topic (as k_match_lds keeps one) costs a wave as
+// many probe rounds per level as its LONGEST frontier (C2: ~1.6 entries per
+// topic on average, but the longest of 64 lanes is 3-4) and the exec-mask
 // bookkeeping of those divergent rounds.  Here the frontier entries of all 64
 // topics of the tile form one list in LDS, {node | FR_PLUS, signature, topic
 // lane}; every round each lane takes the next entry of the list, so a level
 // costs ceil(entries / 64) rounds with every lane busy.  Children are
 // appended to the next level's list with ballot + mbcnt compaction; matches go
-// to the topic's staging column through an LDS counter per topic (one
-// ds_add_rtn per match).  A topic whose entries do not fit the list, or whose
-// row outgrows FAST_MC, is marked (CW_OVF) and queued for the listed pass
-// like k_walk's overflow.  Same hdr / wids input, same stage / cnt / tile-sum
-// output as k_walk, so the listed pass, the scan and k_assemble are shared.
+// to the topic's row through an LDS counter per topic (ds_add_rtn).  A topic whose entries do not fit the list, or whose
+// row outgrows FAST_MC, is marked (CW_OVF) and queued for the listed pass.
 // Frontier entries per wave and level: 9 B each, two lists, so a 4-wave
 // block's LDS is 72 * CW_CAP + 3 KB; 236 keeps it under 20 KB, i.e. 8 blocks
 // (32 waves) per CU in 160 KB.  (192 -> 236 cut C3's list overflow rows; the
@@ -1229,15 +1149,25 @@ __device__ __forceinline__ uint32_t lane_prefix(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0u));
 }
 
-// One wave's walk over its 64-topic tile (k_walk_coop and k_match_fused).
-// h = the topic's tokenizer header; WORDS yields the topic's word id of
-// level 0 (first()) and of the next level (next(level)); the LDS arrays are
-// the wave's own.
+// One wave's walk over its 64-topic tile (coop_walk_tile, below).  h = the
+// topic's tokenizer header; `words` holds the topic's word ids in the lane's
+// registers: of level 0 (first()), of the next level (next()) and of the one
+// after it (peek1()); the LDS arrays are the wave's own.
 struct CoopLds {
   uint2 e[2][CW_CAP];      // {hot id | FR_PLUS, exact-child signature}
   uint8_t ln[2][CW_CAP];   // the entry's topic (lane of the tile)
   uint2 lw[64];            // per topic: {this level's word id, levels | TOK_DOLLAR}
   uint32_t mc[64];         // per topic: matches emitted | CW_OVF
+};
+struct WordsFromRegs {
+  uint32_t (&w)[TOK_LMAX];
+  __device__ __forceinline__ uint32_t peek1() { return w[1]; }  // after next(): the word of level + 2
+  __device__ __forceinline__ uint32_t first() { return w[0]; }
+  __device__ __forceinline__ uint32_t next() {  // shift the levels down: w[0] = the next level's word
+#pragma unroll
+    for (int q = 0; q + 1 < TOK_LMAX; ++q) w[q] = w[q + 1];
+    return w[0];
+  }
 };
 
 // CMP (compact staging, k_match_fused): the tile's matches go to ONE list in
@@ -1355,7 +1285,7 @@ __device__ __forceinline__ D0Probe d0_issue(const IndexView& ix, uint32_t w0, ui
   return p;
 }
 
-// D0 (k_match_fused with IX_D0): level 0 issues no probe of its own.  Each
+// Level 0 under IX_D0 issues no probe of its own.  Each
 // walking lane takes its own topic's root entry, resolves the exact probe its
 // tokenizer issued (d1; parked in the level-0 list's LDS, which a level-0
 // round from registers does not use) and takes the root's '+' child from
@@ -1366,30 +1296,26 @@ __device__ __forceinline__ D0Probe d0_issue(const IndexView& ix, uint32_t w0, ui
 // (l1_bypass / hot_policy), level 0 without IX_D0 -- is compiled in;
 // launch_match picks AB true whenever the call's view or knobs ask for one.
 // FLAT: the tables are read with flat loads (TabRef), chosen per index at launch.
-template <bool EXACT, bool NT, class WORDS, bool CMP = false, bool D0 = false, bool AB = true, bool FLAT = false>
-__device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& words, bool valid, uint64_t t,
+template <bool EXACT, bool NT, bool CMP, bool AB, bool FLAT>
+__device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WordsFromRegs& words, bool valid, uint64_t t,
                                                int lane, const uint8_t* __restrict__ tb,
                                                const uint64_t* __restrict__ toff, const IndexView& ix,
                                                uint32_t* __restrict__ cnt, uint32_t* __restrict__ stage,
                                                uint32_t* __restrict__ ovf_list, uint32_t* __restrict__ ovf_n,
                                                unsigned long long* __restrict__ probe_tile,
                                                unsigned long long* __restrict__ wild_ctr,
-                                               uint64_t* __restrict__ tsum, uint32_t* __restrict__ tlen = nullptr,
-                                               uint8_t* __restrict__ cnt8 = nullptr, PhaseRec* php = nullptr,
-                                               D0Probe d1 = D0Probe{}) {
-  PhaseRec ph_dummy{};
-  PhaseRec& PH = php ? *php : ph_dummy;
+                                               uint64_t* __restrict__ tsum, uint32_t* __restrict__ tlen,
+                                               uint8_t* __restrict__ cnt8, PhaseRec& PH, D0Probe d1) {
   (void)PH;
   constexpr uint32_t MC = FAST_MC;
   constexpr uint32_t TCAP = 64u * FAST_MC;  // a tile's staging entries
-  constexpr bool KC = WORDS::kChain;        // the topic's future words are in its lane's registers
   // d0: the lanes' issued level-0 probes wait in the level-0 list's LDS (a
   // level-0 round from registers reads no list), not in VGPRs: stored first
   // thing, before the wildcard topics' literal lookup needs its registers
   uint4* const D1L = reinterpret_cast<uint4*>(L.e[0]);
   uint32_t* const D1S = reinterpret_cast<uint32_t*>(D1L + 64);
   static_assert(sizeof(L.e[0]) >= 64 * (sizeof(uint4) + 4), "the level-0 list holds 64 probes");
-  const bool d0 = D0 && (!AB || (ix.flags & IX_D0));  // (wave-uniform)
+  const bool d0 = !AB || (ix.flags & IX_D0);  // (wave-uniform)
   if (d0) {
     D1L[lane] = d1.a;
     D1S[lane] = d1.s;
@@ -1457,7 +1383,7 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
   uint64_t tph = __builtin_amdgcn_s_memtime();
   const uint64_t tw0 = tph, tr0w = __builtin_amdgcn_s_memrealtime();
 #endif
-  // One level of the walk (a lambda, so that level 0 under D0 -- the round
+  // One level of the walk (a lambda, so that level 0 under IX_D0 -- the round
   // from registers -- is its own instance and its extra live values do not
   // raise the general loop's register pressure)
   auto walk_level = [&](uint32_t level, auto d0r_tag) {
@@ -1467,9 +1393,8 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
     uint32_t ph_data = 0, ph_rest = 0;
 #endif
     LW[lane] = make_uint2(wnext, nlev | (dollar ? TOK_DOLLAR : 0u));
-    if (walk && level + 1 < nlev) wnext = words.next(level);  // next level's word, in flight
-    uint32_t wnext2 = NONE;  // KC: the word after it (chain nodes of two words)
-    if constexpr (KC) wnext2 = words.peek1();
+    if (walk && level + 1 < nlev) wnext = words.next();  // next level's word
+    const uint32_t wnext2 = words.peek1();  // the word after it (chain nodes of two words)
     wave_lds_sync();
     const uint32_t lvl = __builtin_amdgcn_readfirstlane(level);
     const int ht = hot_table(lvl + 1);
@@ -1556,10 +1481,8 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
       ph_data += uint32_t(tr1 - tr0);
 #endif
       // The topic's next word (its own lane holds it: wnext), for the push
-      // filter and the chain nodes below; the kernel forms without future words
-      // in registers (KC false) push every node with children.
-      uint32_t w1 = NONE;
-      if constexpr (KC) w1 = uint32_t(__builtin_amdgcn_ds_bpermute(int(tl) << 2, int(wnext)));
+      // filter and the chain nodes below
+      const uint32_t w1 = uint32_t(__builtin_amdgcn_ds_bpermute(int(tl) << 2, int(wnext)));
 #ifdef GM_PROBE_STATS
       {
         const unsigned long long c[8] = {__ballot(act), __ballot(st_cand), __ballot(st_sig), __ballot(dx),
@@ -1574,39 +1497,36 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
       // Chain nodes (gm_common.h): the topic must continue with s1 (the head's
       // sig field) and end after the chain's Lc words; the tail {end, s2, -, F}
       // is read (an L2 hit: the head's line was just fetched) only when s1 agrees.
-      const bool chx = KC && ex && !last && (rx.a.w & HOT_CHAIN);
-      const bool chp = KC && ep && !last && (rp.a.w & HOT_CHAIN);
+      const bool chx = ex && !last && (rx.a.w & HOT_CHAIN);
+      const bool chp = ep && !last && (rp.a.w & HOT_CHAIN);
       const bool tx = chx && w1 == rx.a.z, tp = chp && w1 == rp.a.z;
       const uint32_t rem = (lw.y & 0xFFu) - (level + 1);  // the topic's words after this level (>= 1 when !last)
       uint32_t fx = NONE, fp = NONE, vx = 0, vp = 0;  // the chain's filter on a match; virtual probes
-      if constexpr (KC) {
-        if (__ballot(tx || tp)) {
-          GM_PHASE_ADD(13, 1);
-          const uint32_t w2 = uint32_t(__builtin_amdgcn_ds_bpermute(int(tl) << 2, int(wnext2)));
-          uint4 qx{}, qp{};
-          qx = LT.T.template ld128<HS>(hx, 16u, tx, PR_TAIL);
-          qp = LT.T.template ld128<HS>(hp, 16u, tp, PR_TAIL);
-          // the probes the reference NFA makes along the chain (SURVEY §8d's P):
-          // c1 found at level+1 (+2 there if it is the topic's last level,
-          // else +3 for c1's own frontier entry), c2 found at level+2 alike
-          auto chain = [&](const uint4& q, uint32_t& f, uint32_t& vpr) {
-            const uint32_t lc = q.y == NONE ? 1u : 2u;
-            const bool two = lc == 2u && w2 == q.y;
-            if (rem == lc && (lc == 1u || two)) f = q.w;
-            vpr = rem == 1u ? 2u : 3u + (two ? (rem == 2u ? 2u : 3u) : 0u);
-          };
-          if (tx) chain(qx, fx, vx);
-          if (tp) chain(qp, fp, vp);
-        }
+      if (__ballot(tx || tp)) {
+        GM_PHASE_ADD(13, 1);
+        const uint32_t w2 = uint32_t(__builtin_amdgcn_ds_bpermute(int(tl) << 2, int(wnext2)));
+        uint4 qx{}, qp{};
+        qx = LT.T.template ld128<HS>(hx, 16u, tx, PR_TAIL);
+        qp = LT.T.template ld128<HS>(hp, 16u, tp, PR_TAIL);
+        // the probes the reference NFA makes along the chain (SURVEY §8d's P):
+        // c1 found at level+1 (+2 there if it is the topic's last level,
+        // else +3 for c1's own frontier entry), c2 found at level+2 alike
+        auto chain = [&](const uint4& q, uint32_t& f, uint32_t& vpr) {
+          const uint32_t lc = q.y == NONE ? 1u : 2u;
+          const bool two = lc == 2u && w2 == q.y;
+          if (rem == lc && (lc == 1u || two)) f = q.w;
+          vpr = rem == 1u ? 2u : 3u + (two ? (rem == 2u ? 2u : 3u) : 0u);
+        };
+        if (tx) chain(qx, fx, vx);
+        if (tp) chain(qp, fp, vp);
       }
       const bool e5 = fx != NONE && (EXACT || (fx & END_WILD));
       const bool e6 = fp != NONE && (EXACT || (fp & END_WILD));
       // a node goes on to the next level only if one of its probes there can
       // find something: a '+' child, or an exact child the next word's
-      // signature bit admits (KC; otherwise any exact child).  A node that
-      // stays behind (and a chain node) is counted with the probes the
-      // reference NFA would make for it there.
-      const uint32_t b1 = KC ? (w1 != NONE ? sig_bit(w1) : 0u) : 0xFFFFFFFFu;
+      // signature bit admits.  A node that stays behind (and a chain node) is
+      // counted with the probes the reference NFA would make for it there.
+      const uint32_t b1 = w1 != NONE ? sig_bit(w1) : 0u;
       const uint32_t yx = ex ? hot_sig(rx.a.w, rx.a.z) : 0u, yp = ep ? hot_sig(rp.a.w, rp.a.z) : 0u;
       const bool cx = ex && !last && !chx && ((rx.a.w & FR_PLUS) || (yx & b1));
       const bool cp = ep && !last && !chp && ((rp.a.w & FR_PLUS) || (yp & b1));
@@ -1749,62 +1669,15 @@ __device__ __forceinline__ void coop_walk_tile(CoopLds& L, uint32_t h, WORDS& wo
 #endif
 }
 
-
-struct WordsFromHbm {  // k_walk_coop: the tokenizer's level-major word ids
-  static constexpr bool kChain = false;
-  __device__ __forceinline__ uint32_t peek1() { return NONE; }
-  const uint32_t* wp;  // wids + t
-  uint64_t n;
-  bool nt;
-  __device__ __forceinline__ uint32_t first() { return nt ? __builtin_nontemporal_load(wp) : *wp; }
-  __device__ __forceinline__ uint32_t next(uint32_t level) {
-    const uint32_t* p = wp + uint64_t(level + 1) * n;
-    return nt ? __builtin_nontemporal_load(p) : *p;
-  }
-};
-
-template <bool EXACT, bool NT, bool FLAT>
-__global__ __launch_bounds__(256, 8) void k_walk_coop(const uint8_t* __restrict__ tb,
-                                                      const uint64_t* __restrict__ toff, uint64_t n, IndexView ix,
-                                                      const uint32_t* __restrict__ hdr,
-                                                      const uint32_t* __restrict__ wids, uint32_t* __restrict__ cnt,
-                                                      uint32_t* __restrict__ stage, uint32_t* __restrict__ ovf_list,
-                                                      uint32_t* __restrict__ ovf_n,
-                                                      unsigned long long* __restrict__ probe_tile,
-                                                      unsigned long long* __restrict__ wild_ctr,
-                                                      uint64_t* __restrict__ tsum, uint64_t t_base) {
-  __shared__ CoopLds s_w[4];
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const uint64_t t = t_base + uint64_t(blockIdx.x) * 256u + threadIdx.x;
-  if ((t >> 6) * 64 >= n) return;  // wave-uniform: no workgroup barrier below
-  const bool valid = t < n;
-  const uint32_t h = valid ? ld_s<NT>(hdr + t) : 0u;
-  WordsFromHbm words{wids + (valid ? t : 0), n, NT};
-  coop_walk_tile<EXACT, NT, WordsFromHbm, false, false, true, FLAT>(s_w[wv], h, words, valid, t, lane, tb, toff, ix, cnt,
-                                                                    stage, ovf_list, ovf_n, probe_tile, wild_ctr, tsum);
-}
-
 // ---- k_match_fused: tokenize + coop walk in one kernel --------------------
 // The block stages its topics' text in LDS (stage_text: the offsets' loads
 // issued together at entry, then every text load in flight before the first
 // LDS write) and each lane tokenizes its topic
 // into REGISTERS (word ids of up to TOK_LMAX levels, the header); then each
-// wave walks its tile as k_walk_coop does, in the same LDS.  The word ids
-// and headers never go through HBM (k_tokenize + k_walk_coop write and read
-// back ~48 B per C2 topic of them), and the tokenizer's ALU work of one wave
-// overlaps the walk's gathers of the others.
-struct WordsFromRegs {
-  static constexpr bool kChain = true;
-  uint32_t (&w)[TOK_LMAX];
-  __device__ __forceinline__ uint32_t peek1() { return w[1]; }  // after next(level): the word of level + 2
-  __device__ __forceinline__ uint32_t first() { return w[0]; }
-  __device__ __forceinline__ uint32_t next(uint32_t) {  // shift the levels down: w[0] = the next level's word
-#pragma unroll
-    for (int q = 0; q + 1 < TOK_LMAX; ++q) w[q] = w[q + 1];
-    return w[0];
-  }
-};
-
+// wave walks its tile (coop_walk_tile) in the same LDS.  The word ids and
+// headers never go through HBM (as two kernels they cost ~48 B per C2 topic,
+// written and read back), and the tokenizer's ALU work of one wave overlaps
+// the walk's gathers of the others.
 constexpr size_t FUSED_LDS = sizeof(CoopLds) * 4 > (TOK_STAGE + 8) ? sizeof(CoopLds) * 4 : (TOK_STAGE + 8);
 
 // Two uniform 8-byte loads issued together, one wait for both (left to the
@@ -1860,7 +1733,7 @@ __device__ __forceinline__ void stage_text(uint64_t* dst, const uint8_t* src, ui
 }
 
 // AB, FLAT: coop_walk_tile's (the default instantiation is AB false, FLAT false)
-template <int G, bool EXACT, bool NT, bool TOKPRIO, bool CMP, bool AB, bool FLAT, bool D0 = true>
+template <bool EXACT, bool NT, bool TOKPRIO, bool CMP, bool AB, bool FLAT>
 __global__ __launch_bounds__(256, 8) void k_match_fused(const uint8_t* __restrict__ tb,
                                                         const uint64_t* __restrict__ toff, uint64_t n, IndexView ix,
                                                         uint32_t* __restrict__ cnt, uint32_t* __restrict__ stage,
@@ -1911,7 +1784,7 @@ __global__ __launch_bounds__(256, 8) void k_match_fused(const uint8_t* __restric
   uint32_t h = 0;
   if (valid) {
     if (staged) {
-      h = tokenize_grouped<G, !FLAT>(s_txt, uint32_t(pos - lo), uint32_t(end - lo), ix, tb + lo, WidsToRegs{w});
+      h = tokenize_grouped<TOK_GROUP, !FLAT>(s_txt, uint32_t(pos - lo), uint32_t(end - lo), ix, tb + lo, WidsToRegs{w});
     } else {
       ByteReader rd{tb, ~0ull, 0};
       h = tokenize_topic(rd, pos, end, ix, tb, WidsToRegs{w});
@@ -1927,7 +1800,7 @@ __global__ __launch_bounds__(256, 8) void k_match_fused(const uint8_t* __restric
   // issued before the walk's setup and resolved in its level-0 round (held
   // across the block barrier it spilled)
   D0Probe d1{make_uint4(0u, 0u, 0u, 0u), NONE};
-  if (D0 && (!AB || (ix.flags & IX_D0))) d1 = d0_issue<FLAT>(ix, w[0], h, valid);
+  if (!AB || (ix.flags & IX_D0)) d1 = d0_issue<FLAT>(ix, w[0], h, valid);
   WordsFromRegs words{w};
   // the walk's topic index, formed again from the wave's scalar base (hidden
   // from value numbering) so that the front end's copy is not held in two
@@ -1935,9 +1808,8 @@ __global__ __launch_bounds__(256, 8) void k_match_fused(const uint8_t* __restric
   uint32_t twl = uint32_t(tw), twh = uint32_t(tw >> 32);
   asm volatile("" : "+s"(twl), "+s"(twh));
   const uint64_t t_w = (uint64_t(twh) << 32) | (twl | uint32_t(lane));
-  coop_walk_tile<EXACT, NT, WordsFromRegs, CMP, D0, AB, FLAT>(reinterpret_cast<CoopLds*>(s_raw)[wv], h, words, valid, t_w, lane,
-                                                    tb, toff, ix, cnt, stage, ovf_list, ovf_n, probe_tile, wild_ctr,
-                                                    tsum, tlen, cnt8, &PH, d1);
+  coop_walk_tile<EXACT, NT, CMP, AB, FLAT>(reinterpret_cast<CoopLds*>(s_raw)[wv], h, words, valid, t_w, lane, tb, toff, ix,
+                                           cnt, stage, ovf_list, ovf_n, probe_tile, wild_ctr, tsum, tlen, cnt8, PH, d1);
 }
 
 // ---- the match call's pass counters; its scan is gm_scan.h's scan_excl -----
@@ -2423,17 +2295,14 @@ namespace {
 
 // Main-pass kernel selection.  GM_MATCH_MAIN (A/B knob, read per call so tests
 // cover every kind): fused (k_match_fused: tokenizer into registers + the
-// compacted wave walk in one kernel, default; C2 10.2 ms vs 12.0 for the
-// split coop pair), coop (k_tokenize + k_walk_coop, the wave's frontier as
-// one compacted list), splitw8 (k_tokenize + k_walk, lane-private register
-// frontier, 8-wave register budget), split (budget left to the compiler),
-// split2 (k_walk expanding frontier entries in pairs).
-enum MainKind { MAIN_SPLIT, MAIN_SPLITW8, MAIN_SPLIT2, MAIN_COOP, MAIN_FUSED };
+// compacted wave walk in one kernel, default), splitw8 (k_tokenize + k_walk,
+// lane-private register frontier, 8-wave register budget), split (budget left
+// to the compiler).
+enum MainKind { MAIN_SPLIT, MAIN_SPLITW8, MAIN_FUSED };
 MainKind main_kind() {
   const char* e = knob("GM_MATCH_MAIN");
   static const struct { const char* name; MainKind kind; } names[] = {
-      {"split", MAIN_SPLIT}, {"splitw8", MAIN_SPLITW8}, {"split2", MAIN_SPLIT2}, {"coop", MAIN_COOP},
-      {"fused", MAIN_FUSED}};
+      {"split", MAIN_SPLIT}, {"splitw8", MAIN_SPLITW8}, {"fused", MAIN_FUSED}};
   if (e)
     for (const auto& nk : names)
       if (!strcmp(e, nk.name)) return nk.kind;
@@ -2528,136 +2397,91 @@ void launch_tokenize(hipStream_t st, uint64_t nblk, const uint8_t* tb, const uin
 #undef GM_TOK
 }
 
-// Tokenize / walk overlap.  GM_OVERLAP = K (A/B knob, read per call; 1 = off):
-// the batch is cut into K block ranges; chunk i is tokenized on a second
-// stream while the walk of chunk i-1 runs on the context's stream (the
-// tokenizer is VALU bound, the walk waits on the fabric, so the two can share
-// the CUs).  Kernels index by t_base + their own grid, so the layouts are
-// those of one launch.
-int overlap_chunks() {
-  const char* e = knob("GM_OVERLAP");
-  const int v = e ? atoi(e) : 1;
-  return v < 1 ? 1 : (v > 8 ? 8 : v);
-}
-
-// Main pass, then the listed pass over its overflow queue (count read on the
-// device).  `after_main` is recorded between the two: the roofline times the
-// main pass alone, the same kernel rocprofv3 reports.
+// The listed pass over the main pass's overflow queue (list1, its count n1 on the device)
 template <bool EXACT>
 void launch_listed(hipStream_t st, const IndexView& v, const uint8_t* tb, const uint64_t* to, uint64_t n, uint32_t* cnt,
                    uint32_t* stage, uint32_t* list1, uint32_t* n1, uint32_t* list2, uint32_t* n2,
-                   unsigned long long* probe_ctr, unsigned long long* wild_ctr, uint64_t* tsum, const CmpBufs* cb);
+                   unsigned long long* probe_ctr, unsigned long long* wild_ctr, uint64_t* tsum, const CmpBufs* cb) {
+  const uint64_t nblk = (n + 255) / 256;
+  const uint64_t lblk = std::min<uint64_t>(nblk, 512);
+  if (cb)
+    hipLaunchKernelGGL((k_match_lds<EXACT, LISTED_FC, true>), dim3(lblk), dim3(256), 0, st, tb, to, n, v, cnt, stage,
+                       list1, n1, list2, n2, probe_ctr, wild_ctr, tsum, cb->lstage, cb->lcnt, cb->lcap);
+  else
+    hipLaunchKernelGGL((k_match_lds<EXACT, LISTED_FC, false>), dim3(lblk), dim3(256), 0, st, tb, to, n, v, cnt, stage,
+                       list1, n1, list2, n2, probe_ctr, wild_ctr, tsum, nullptr, nullptr, 0);
+}
+
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a template argument
+template <class F>
+void with_flag(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// Main pass, then the listed pass over its overflow queue (count read on the
+// device).  before_main / after_main (both null for an untimed call,
+// EMQX_GM_NO_TIMING) take the main pass's own start and stop: the roofline
+// times the main pass alone, the same kernel rocprofv3 reports.
 template <bool EXACT>
-void launch_match(emqx_gm_ctx* ctx, const IndexView& v, const uint8_t* tb, const uint64_t* to, uint64_t n,
+void launch_match(hipStream_t st, const IndexView& v, const uint8_t* tb, const uint64_t* to, uint64_t n,
                   uint32_t* cnt, uint32_t* stage, uint32_t* list1, uint32_t* n1, uint32_t* list2, uint32_t* n2,
                   unsigned long long* probe_ctr, unsigned long long* wild_ctr, uint32_t* hdr, uint32_t* wids,
                   unsigned long long* probe_tile, uint64_t* tsum, hipEvent_t before_main, hipEvent_t after_main,
                   const CmpBufs* cb, bool* listed_deferred) {
-  hipStream_t st = ctx->stream;
   const uint64_t nblk = (n + 255) / 256;
   *listed_deferred = false;
-  const bool flat = view_flat(v);  // a table too large for 32-bit byte offsets: the flat instantiations
-#define GM_LAUNCH_WALK(W, P, sw, g, base)                                                                        \
-  hipLaunchKernelGGL((k_walk<EXACT, W, P>), dim3(g), dim3(256), 0, sw, tb, to, n, v, hdr, wids, cnt, stage, list1, n1, \
-                     probe_tile, wild_ctr, tsum, base)
-#define GM_LAUNCH_COOP(NT, FL, sw, g, base)                                                                      \
-  hipLaunchKernelGGL((k_walk_coop<EXACT, NT, FL>), dim3(g), dim3(256), 0, sw, tb, to, n, v, hdr, wids, cnt, stage, list1, \
-                     n1, probe_tile, wild_ctr, tsum, base)
-#define GM_WALK(sw, g, base)                                  \
-  do {                                                        \
-    switch (main_kind()) {                                    \
-      case MAIN_SPLIT: GM_LAUNCH_WALK(1, false, sw, g, base); break;  \
-      case MAIN_SPLIT2: GM_LAUNCH_WALK(1, true, sw, g, base); break;  \
-      case MAIN_COOP:                                         \
-        if (nt_streams() && flat)                             \
-          GM_LAUNCH_COOP(true, true, sw, g, base);            \
-        else if (nt_streams())                                \
-          GM_LAUNCH_COOP(true, false, sw, g, base);           \
-        else if (flat)                                        \
-          GM_LAUNCH_COOP(false, true, sw, g, base);           \
-        else                                                  \
-          GM_LAUNCH_COOP(false, false, sw, g, base);          \
-        break;                                                \
-      default: GM_LAUNCH_WALK(8, false, sw, g, base);         \
-    }                                                         \
-  } while (0)
-  int K = overlap_chunks();
-  if (K > 1 && nblk < uint64_t(K) * 1024) K = 1;  // small batches: one launch each
-  if (K > 1 && !ctx->stream2 && hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess) {
-    ctx->stream2 = nullptr;
-    K = 1;
+  const MainKind kind = main_kind();
+  if (kind != MAIN_FUSED) {
+    // the split A/B forms: events recorded around the two launches (cb is null: no compact staging)
+    hipEventRecord(before_main, st);
+    launch_tokenize(st, nblk, tb, to, n, v, hdr, wids, 0);
+    auto walk = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(nblk), dim3(256), 0, st, tb, to, n, v, hdr, wids, cnt, stage, list1, n1, probe_tile,
+                         wild_ctr, tsum, uint64_t(0));
+    };
+    if (kind == MAIN_SPLIT) walk(k_walk<EXACT, 1>);
+    else walk(k_walk<EXACT, 8>);
+    hipEventRecord(after_main, st);
+    launch_listed<EXACT>(st, v, tb, to, n, cnt, stage, list1, n1, list2, n2, probe_ctr, wild_ctr, tsum, cb);
+    return;
   }
-  for (int i = 0; K > 1 && i <= K; ++i)
-    if (!ctx->ov_ev[i] && hipEventCreateWithFlags(&ctx->ov_ev[i], hipEventDisableTiming) != hipSuccess) K = 1;
 #ifdef GM_PHASE_STATS
   uint32_t* phase_rec = nullptr;
-  if (main_kind() == MAIN_FUSED && n && hipStreamSynchronize(st) == hipSuccess &&
-      hipMalloc(&phase_rec, (n + 63) / 64 * 128) == hipSuccess) {
+  if (n && hipStreamSynchronize(st) == hipSuccess && hipMalloc(&phase_rec, (n + 63) / 64 * 128) == hipSuccess) {
     (void)hipMemset(phase_rec, 0, (n + 63) / 64 * 128);
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_phase_rec), &phase_rec, sizeof phase_rec);
   }
 #endif
-  if (main_kind() == MAIN_FUSED) {
-    const char* pe = knob("GM_FUSED_PRIO");  // A/B knob (read per call): 0 = every phase at priority 0
-    const bool tp = !pe || atoi(pe) != 0;
-    uint32_t* const tl = cb ? cb->tlen : nullptr;
-    uint8_t* const c8 = cb ? cb->cnt8 : nullptr;
-    // the kernel's own start / stop timestamps (hipExtLaunchKernel) instead of
-    // two event records around it: each record is a barrier packet that costs
-    // the stream ~5.5 us of idle GPU (C1 per-call trace, profiles/r03_c1_trace.txt)
-#define GM_FUSED(NT, P, C)                                             \
-  do {                                                                 \
-    if (flat) GM_FUSED_K(NT, P, C, true, true);                        \
-    else GM_FUSED_K(NT, P, C, true, false);                            \
-  } while (0)
-#define GM_FUSED_K(NT, P, C, AB, FL)                                                                                \
-  hipExtLaunchKernelGGL((k_match_fused<3, EXACT, NT, P, C, AB, FL>), dim3(nblk), dim3(256), 0, st, kt ? before_main : nullptr,   \
-                        kt ? after_main : nullptr, 0,                                                                     \
-                        tb, to, n, v, cnt, stage, list1, n1, probe_tile, wild_ctr, tsum, tl, c8)
-    const bool kt = before_main != nullptr;  // (an untimed call: EMQX_GM_NO_TIMING)
-    // The default instantiation (AB false): default knobs, a view that asks for
-    // no A/B form and buffer-sized tables.  Everything else runs the general one.
-    const bool plain = nt_streams() && tp && !flat && (v.flags & IX_D0) && !(v.flags & IX_STAGE_SC1) && !v.l1_bypass;
+  const bool nt = nt_streams();
+  const char* pe = knob("GM_FUSED_PRIO");  // A/B knob (read per call): 0 = every phase at priority 0
+  const bool prio = !pe || atoi(pe) != 0;
+  const bool flat = view_flat(v);  // a table too large for 32-bit byte offsets: the flat instantiations
+  // The kernel's own start / stop timestamps (hipExtLaunchKernel) instead of
+  // two event records around it: each record is a barrier packet that costs
+  // the stream ~5.5 us of idle GPU (C1 per-call trace, profiles/r03_c1_trace.txt)
+  auto launch = [&](auto kernel) {
+    hipExtLaunchKernelGGL(kernel, dim3(nblk), dim3(256), 0, st, before_main, after_main, 0, tb, to, n, v, cnt, stage, list1,
+                          n1, probe_tile, wild_ctr, tsum, cb ? cb->tlen : nullptr, cb ? cb->cnt8 : nullptr);
+  };
+  // k_match_fused<EXACT, NT, TOKPRIO, CMP, AB, FLAT>.  The default instantiation
+  // (AB false): default knobs, a view that asks for no A/B form and
+  // buffer-sized tables.  Everything else runs the general one (AB true).
+  const bool plain = nt && prio && !flat && (v.flags & IX_D0) && !(v.flags & IX_STAGE_SC1) && !v.l1_bypass;
+  with_flag(cb != nullptr, [&](auto cmp) {
+    constexpr bool CMP = decltype(cmp)::value;
     if (plain) {
-      if (cb) GM_FUSED_K(true, true, true, false, false);
-      else GM_FUSED_K(true, true, false, false, false);
-    } else if (cb) {
-      if (nt_streams() && tp) GM_FUSED(true, true, true);
-      else if (nt_streams()) GM_FUSED(true, false, true);
-      else if (tp) GM_FUSED(false, true, true);
-      else GM_FUSED(false, false, true);
-    } else if (nt_streams()) {
-      if (tp) GM_FUSED(true, true, false);
-      else GM_FUSED(true, false, false);
-    } else {
-      if (tp) GM_FUSED(false, true, false);
-      else GM_FUSED(false, false, false);
+      launch(k_match_fused<EXACT, true, true, CMP, false, false>);
+      return;
     }
-#undef GM_FUSED
-#undef GM_FUSED_K
-  } else if (K == 1) {
-    hipEventRecord(before_main, st);
-    launch_tokenize(st, nblk, tb, to, n, v, hdr, wids, 0);
-    GM_WALK(st, nblk, 0ull);
-  } else {
-    hipEventRecord(before_main, st);
-    hipStream_t st2 = ctx->stream2;
-    hipEventRecord(ctx->ov_ev[0], st);  // the tokenizer stream starts after the work queued so far
-    hipStreamWaitEvent(st2, ctx->ov_ev[0], 0);
-    const uint64_t cb = (nblk + K - 1) / K;
-    for (int i = 0; i < K; ++i) {
-      const uint64_t b0 = uint64_t(i) * cb;
-      if (b0 >= nblk) break;
-      const uint64_t nb = std::min<uint64_t>(cb, nblk - b0);
-      launch_tokenize(st2, nb, tb, to, n, v, hdr, wids, b0 * 256);
-      hipEventRecord(ctx->ov_ev[i + 1], st2);
-      hipStreamWaitEvent(st, ctx->ov_ev[i + 1], 0);
-      GM_WALK(st, nb, b0 * 256);
-    }
-  }
-#undef GM_WALK
-#undef GM_LAUNCH_COOP
-#undef GM_LAUNCH_WALK
+    with_flag(nt, [&](auto nt_) {
+      with_flag(prio, [&](auto prio_) {
+        with_flag(flat, [&](auto flat_) {
+          launch(k_match_fused<EXACT, decltype(nt_)::value, decltype(prio_)::value, CMP, true, decltype(flat_)::value>);
+        });
+      });
+    });
+  });
 #ifdef GM_PROBE_STATS
   {
     unsigned long long h[8][8], z[8][8] = {};
@@ -2698,13 +2522,12 @@ void launch_match(emqx_gm_ctx* ctx, const IndexView& v, const uint8_t* tb, const
     (void)hipFree(phase_rec);
   }
 #endif
-  if (main_kind() != MAIN_FUSED) hipEventRecord(after_main, st);
-  (void)probe_tile;  // summed into the probe counter by the tile scan (run_match)
-  // The fused main pass with compact staging leaves the listed pass to the
-  // host's read-back (MatchCall::finish): it launches it only when the main
-  // pass queued rows, instead of an (almost always idle) launch per call.
+  // (probe_tile is summed into the probe counter by the tile scan, MatchCall::submit)
+  // With compact staging the listed pass is left to the host's read-back
+  // (MatchCall::finish): it launches it only when the main pass queued rows,
+  // instead of an (almost always idle) launch per call.
   // GM_LISTED_DEFER=0: launch it here (A/B knob).
-  if (cb && main_kind() == MAIN_FUSED) {
+  if (cb) {
     const char* le = knob("GM_LISTED_DEFER");
     if (!le || atoi(le) != 0) {
       *listed_deferred = true;
@@ -2712,21 +2535,6 @@ void launch_match(emqx_gm_ctx* ctx, const IndexView& v, const uint8_t* tb, const
     }
   }
   launch_listed<EXACT>(st, v, tb, to, n, cnt, stage, list1, n1, list2, n2, probe_ctr, wild_ctr, tsum, cb);
-}
-
-// The listed pass over the main pass's overflow queue (list1, its count n1 on the device)
-template <bool EXACT>
-void launch_listed(hipStream_t st, const IndexView& v, const uint8_t* tb, const uint64_t* to, uint64_t n, uint32_t* cnt,
-                   uint32_t* stage, uint32_t* list1, uint32_t* n1, uint32_t* list2, uint32_t* n2,
-                   unsigned long long* probe_ctr, unsigned long long* wild_ctr, uint64_t* tsum, const CmpBufs* cb) {
-  const uint64_t nblk = (n + 255) / 256;
-  const uint64_t lblk = std::min<uint64_t>(nblk, 512);
-  if (cb)
-    hipLaunchKernelGGL((k_match_lds<EXACT, LISTED_FC, true, true>), dim3(lblk), dim3(256), 0, st, tb, to, n, v, cnt,
-                       stage, list1, n1, list2, n2, probe_ctr, wild_ctr, tsum, cb->lstage, cb->lcnt, cb->lcap);
-  else
-    hipLaunchKernelGGL((k_match_lds<EXACT, LISTED_FC, true>), dim3(lblk), dim3(256), 0, st, tb, to, n, v, cnt, stage,
-                       list1, n1, list2, n2, probe_ctr, wild_ctr, tsum);
 }
 
 }  // namespace
@@ -2895,7 +2703,8 @@ int MatchCall::submit(const emqx_gm_index* index, const uint8_t* tb_in, const ui
   probe_tile = PoolBuf(ctx->pool, n_tiles * 8 + 8);
   if (!probe_tile.p) return set_err(ctx, EMQX_GM_ENOMEM, "match: probe workspace");
   // split forms: per-topic header and word ids [level][topic] (the fused kernel keeps them in registers)
-  if (main_kind() != MAIN_FUSED) {
+  const bool fused = main_kind() == MAIN_FUSED;
+  if (!fused) {
     hdr = PoolBuf(ctx->pool, n * 4 + 16);
     wids = PoolBuf(ctx->pool, uint64_t(TOK_LMAX) * n * 4 + 16);
     if (!hdr.p || !wids.p) return set_err(ctx, EMQX_GM_ENOMEM, "match: word-id workspace");
@@ -2910,7 +2719,7 @@ int MatchCall::submit(const emqx_gm_index* index, const uint8_t* tb_in, const ui
   // before the main pass can be queued, a launch ~6)
   if (zero_ctrs) hipLaunchKernelGGL(k_zero16, dim3(1), dim3(64), 0, st, reinterpret_cast<uint32_t*>(ctrs_p));
 
-  cmp = main_kind() == MAIN_FUSED && stage_compact() && uint64_t(idx->view.n_filters) < (1ull << CMP_SHIFT);
+  cmp = fused && stage_compact() && uint64_t(idx->view.n_filters) < (1ull << CMP_SHIFT);
   if (cmp) {
     const char* le = knob("GM_LISTED_CAP");  // (tests: listed rows past it go to the slow path)
     cmpb.lcap = std::min<uint64_t>(n, le ? strtoull(le, nullptr, 10) : (1u << 20));
@@ -2926,7 +2735,7 @@ int MatchCall::submit(const emqx_gm_index* index, const uint8_t* tb_in, const ui
   }
   // ev[0] / ev[1]: the main pass's start and end (also the call's start: total_device_ms);
   // an untimed call of the fused pass launches it without them
-  if (main_kind() != MAIN_FUSED) timed = true;  // (the other forms record their events around the launches)
+  if (!fused) timed = true;  // (the split forms record their events around the launches)
   hipEvent_t main_ev0 = ev[0], main_ev1 = ev[1];
   if (!timed) main_ev0 = main_ev1 = nullptr;
   // GM_D0=0 (A/B knob, read per call): level 0 probed like any other level
@@ -2939,13 +2748,13 @@ int MatchCall::submit(const emqx_gm_index* index, const uint8_t* tb_in, const ui
   if (const char* pe = knob("GM_HOT_POLICY")) vcall.hot_policy = uint32_t(strtoul(pe, nullptr, 0));
   if (knob("GM_HOT_FLAT")) vcall.flags |= IX_HOT_FLAT;  // (test knob, also read per call: the flat instantiation)
   if (exact)
-    launch_match<true>(ctx, vcall, tb, to, n, cnt.as<uint32_t>(), stage.as<uint32_t>(), list1.as<uint32_t>(), n1,
+    launch_match<true>(st, vcall, tb, to, n, cnt.as<uint32_t>(), stage.as<uint32_t>(), list1.as<uint32_t>(), n1,
                        list2.as<uint32_t>(), n2, probe_ctr, wild_ctr, hdr.as<uint32_t>(), wids.as<uint32_t>(),
                        probe_tile.as<unsigned long long>(), tsum.as<uint64_t>(), main_ev0, main_ev1,
                        cmp ? &cmpb : nullptr, &listed_deferred);
   else
-    launch_match<false>(ctx, vcall, tb, to, n, cnt.as<uint32_t>(), stage.as<uint32_t>(), list1.as<uint32_t>(),
-                        n1, list2.as<uint32_t>(), n2, probe_ctr, wild_ctr, hdr.as<uint32_t>(), wids.as<uint32_t>(),
+    launch_match<false>(st, vcall, tb, to, n, cnt.as<uint32_t>(), stage.as<uint32_t>(), list1.as<uint32_t>(), n1,
+                        list2.as<uint32_t>(), n2, probe_ctr, wild_ctr, hdr.as<uint32_t>(), wids.as<uint32_t>(),
                         probe_tile.as<unsigned long long>(), tsum.as<uint64_t>(), main_ev0, main_ev1,
                         cmp ? &cmpb : nullptr, &listed_deferred);
   GM_HIP(ctx, hipGetLastError());
@@ -2957,7 +2766,7 @@ int MatchCall::submit(const emqx_gm_index* index, const uint8_t* tb_in, const ui
   // walk's tail.  (Its pass counters were zeroed on the context stream; the
   // assembly then zeroes no ring block for a later call.)
   hipStream_t sa = st;
-  if (asm_overlap && main_kind() == MAIN_FUSED) {
+  if (asm_overlap && fused) {
     if (!ctx->stream_asm && hipStreamCreateWithFlags(&ctx->stream_asm, hipStreamNonBlocking) != hipSuccess)
       ctx->stream_asm = nullptr;
     if (ctx->stream_asm) {

@@ -43,7 +43,8 @@ def function_body(lines, subs):
 
 def main():
     path = sys.argv[1]
-    subs = sys.argv[2:] or ["13k_match_fusedILi3ELb1ELb1ELb1ELb1E"]
+    # k_match_fused<EXACT, NT, TOKPRIO, CMP, AB = false, FLAT = false>
+    subs = sys.argv[2:] or ["13k_match_fusedILb1ELb1ELb1ELb1ELb0ELb0EE"]
     name, body = function_body(open(path).read().splitlines(), subs)
     ins = []
     for ln in body:

@@ -591,8 +591,8 @@ def test_tokenizer_groups(ctx, orc, monkeypatch, group):
     trailing '/', and topics deeper than the 8 tokenized levels must give
     the same rows as the oracle for every G.  k_tokenize runs only under the
     split main passes (the default fused kernel tokenizes into registers, always
-    three levels at a time), so every G is run under GM_MATCH_MAIN=coop
-    (k_walk_coop) and splitw8 (k_walk), and under the default as before."""
+    three levels at a time), so every G is run under GM_MATCH_MAIN=splitw8
+    (k_walk), and under the default as before."""
     monkeypatch.setenv("GM_TOK_GROUP", group)
     rng = random.Random(23)
     words = [b"a", b"b", b"", b"cc", b"longword_over_8_bytes", b"$SYS", b"d"]
@@ -610,45 +610,11 @@ def test_tokenizer_groups(ctx, orc, monkeypatch, group):
         if rng.random() < 0.1:  # a wildcard word at any level, including past the group / 8-level bounds
             lev[rng.randrange(n)] = rng.choice([b"+", b"#"])
         topics.append(b"/".join(lev))
-    for main in (None, "coop", "splitw8"):
+    for main in (None, "splitw8"):
         if main:
             monkeypatch.setenv("GM_MATCH_MAIN", main)
         _check(ctx, orc, sorted(filters), topics, True)
         _check(ctx, orc, filters, topics, False)
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("chunks", ["2", "3"])
-def test_overlapped_match_equals_single_launch(ctx, orc, monkeypatch, chunks):
-    """GM_OVERLAP=K (tokenizer of chunk i on a second stream while the walk of
-    chunk i-1 runs): the CSR must be bit-identical to the one-launch result
-    (itself checked against the oracle above), and a strided sample of rows
-    must equal the oracle's.  The knob is read by the split main passes only:
-    the test runs k_tokenize + k_walk_coop (GM_MATCH_MAIN=coop), and the host
-    batch as one chunk (the default 256K-topic chunks are 1,024 blocks each,
-    under the K * 1,024 blocks the chunked launch needs)."""
-    from emqx_amd.engine import gen_filter_codes, render_codes
-    monkeypatch.setenv("GM_MATCH_MAIN", "coop")
-    monkeypatch.setenv("GM_HOST_CHUNK", "4194304")
-    codes = gen_filter_codes(3, 20000, wildcard_only=True)
-    fb, fo = render_codes(codes)
-    filters = orc.unpack(fb, fo)
-    idx = ctx.build_index(sorted(set(filters)))
-    n = 1_300_000  # > K * 1024 blocks of 256 topics, so the chunked path runs
-    tb, to = orc.render_codes(orc.gen_topic_codes(3, 0, n, codes))
-    monkeypatch.setenv("GM_OVERLAP", "1")
-    ro1, ids1 = ctx.match(idx, (tb, to), exact=True)
-    monkeypatch.setenv("GM_OVERLAP", chunks)
-    ro2, ids2 = ctx.match(idx, (tb, to), exact=True)
-    assert np.array_equal(ro1, ro2) and np.array_equal(ids1, ids2)
-    sample = list(range(0, n, 997))
-    topics = orc.unpack(tb, to)
-    sub = [topics[i] for i in sample]
-    fl = sorted(set(filters))
-    oro, oids = _oracle_rows(orc, fl, sub, 1)
-    for j, i in enumerate(sample):
-        assert ids2[ro2[i]:ro2[i + 1]].tolist() == oids[oro[j]:oro[j + 1]].tolist(), topics[i]
-    idx.release()
 
 
 @pytest.mark.gpu

@@ -264,9 +264,9 @@ def test_chain_nodes_every_length(ctx, orc, chain, form, monkeypatch):
 # ------------------------------------------------------------------ kernel forms
 KERNEL_FORMS = [{}, {"GM_STAGE_COMPACT": "0"}, {"GM_D0": "0"}, {"GM_STAGE_SC1": "1"}, {"GM_HOT_FLAT": "1"},
                 {"GM_FUSED_PRIO": "0"}, {"GM_NT": "0"}, {"GM_NT": "0", "GM_STAGE_COMPACT": "0"}]
-KERNEL_FORMS += [{"GM_MATCH_MAIN": m, "GM_TOK_GROUP": g} for m in ("coop", "split", "splitw8", "split2")
+KERNEL_FORMS += [{"GM_MATCH_MAIN": m, "GM_TOK_GROUP": g} for m in ("split", "splitw8")
                  for g in ("1", "3", "5")]
-KERNEL_FORMS += [{"GM_MATCH_MAIN": m, "GM_NT": "0"} for m in ("coop", "splitw8")]
+KERNEL_FORMS += [{"GM_MATCH_MAIN": "splitw8", "GM_NT": "0"}]
 
 
 def _form_id(env):
@@ -277,7 +277,7 @@ def _form_id(env):
 @pytest.mark.parametrize("chains", [False, True], ids=["plain", "chains"])
 def test_kernel_forms(ctx, orc, base, env, chains, monkeypatch):
     """Every main-pass kernel and instantiation: k_match_fused with each A/B
-    form, k_tokenize<1|3|5> + k_walk_coop / k_walk<1|8, pair>, nt and plain
+    form, k_tokenize<1|3|5> + k_walk<1|8>, nt and plain
     streams; rows against the oracle and the counters against the reference."""
     if chains:
         monkeypatch.setenv("GM_CHAIN", "1")
@@ -439,7 +439,7 @@ def _overflow_case():
     return ref, tiles, set(heavy) | {NARROW}
 
 
-@pytest.mark.parametrize("main", ["fused", "fused_columns", "coop", "splitw8"])
+@pytest.mark.parametrize("main", ["fused", "fused_columns", "splitw8"])
 def test_overflow_rows_bounds_and_slow_count(ctx, orc, main, monkeypatch):
     """Tiles of light topics beside tiles of topics with more than 16 matches
     (past FAST_MC: the main and the listed pass give them up, the slow path
@@ -450,7 +450,7 @@ def test_overflow_rows_bounds_and_slow_count(ctx, orc, main, monkeypatch):
     -- and n_overflow is the rows the slow path completed: the heavy ones.
 
     Measured on an MI355X, this batch (613 topics, sum P(light) = 6,760, sum
-    P(heavy) = 54,264): probes = 55,865 with the fused and the coop main pass,
+    P(heavy) = 54,264): probes = 55,865 with the fused main pass,
     37,477 with k_walk, which zeroes the count of a topic it gives up (the
     18,388 between them are what coop_walk_tile keeps of the heavy rows; it
     accumulates per entry lane and cannot take a topic's count back).  Both
