@@ -31,12 +31,8 @@
 //   k_d0_refresh   the walk's level-0 record (IndexView::d0_root), rewritten
 //                  at build and after each in-place update (refresh_d0).
 //
-//   k_tokenize + k_walk
-//                  the main pass as two kernels through HBM word ids, k_walk
-//                  with a lane-private frontier in registers (A/B forms,
-//                  GM_MATCH_MAIN=split|splitw8).
-// The wave-cooperative walk as a kernel of its own behind k_tokenize
-// (k_walk_coop) and the two-stream tokenize/walk overlap (GM_OVERLAP) are gone;
+// k_match_fused is the only main pass.  The earlier forms of it as two kernels
+// through word ids in HBM, and the two-stream tokenize/walk overlap, are gone;
 // DESIGN.md section 4 keeps their measurements against the fused kernel.
 //
 // Everything here is integer/byte work bound by HBM/L2 latency and bandwidth;
@@ -47,7 +43,6 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <type_traits>
 #include <vector>
 
@@ -60,7 +55,7 @@ namespace gm {
 // device helpers
 // ---------------------------------------------------------------------------
 
-// Stream accesses (topic text, word ids, headers, staging, counts, the CSR)
+// Stream accesses (topic text, staging, counts, the CSR)
 // touch each byte once; NT = non-temporal, so they do not evict the index
 // tables from L2 / the Infinity Cache (GM_NT knob, A/B).
 template <bool NT, class T>
@@ -399,7 +394,7 @@ __device__ __forceinline__ void stage_st(uint32_t* base, uint32_t k, uint32_t v,
   }
 }
 
-// ---- the row, visit and probe steps of the lane-private walks (k_match_lds, k_walk) ----
+// ---- the row, visit and probe steps of the lane-private walk (k_match_lds) ----
 // Per-lane match staging: emit one filter id into the topic's row (slot m_n
 // of the topic's lane column in its tile, srow = &stage[stage_index(tile, 0,
 // lane)]; or of its listed row).
@@ -441,13 +436,6 @@ __device__ __forceinline__ void stage_st(uint32_t* base, uint32_t k, uint32_t v,
       }                                                      \
     }                                                        \
   } while (0)
-
-// Frontier of k_walk: at most RFC entries {hot id | FR_PLUS, exact-child
-// signature} in registers (pushes are select chains over static indices, so
-// nothing spills to scratch).  A lane whose frontier outgrows RFC, or whose row
-// outgrows FAST_MC, is queued for the listed pass and contributes nothing
-// in the main pass.
-constexpr int RFC = 4;
 
 // The record of the '+' child held inline by slot `id` of its parent's table
 // (gm_common.h): the slot's second 16 bytes, a line this walk read one level
@@ -631,15 +619,18 @@ __global__ __launch_bounds__(256) void k_match_lds(const uint8_t* __restrict__ t
   if (lane == 0 && ptot) atomicAdd(probe_ctr, (unsigned long long)ptot);
 }
 #undef GM_PUSH
+#undef GM_PROBE_ISSUE
+#undef GM_PROBE_TAKE
+#undef GM_VISIT
+#undef GM_WILD_ROW
+#undef GM_EMIT
 
-// ---- the tokenizer ------------------------------------------------------------
+// ---- the tokenizer (k_match_fused's front end) ----------------------------------
 // Per topic: a header = levels | TOK_DOLLAR | TOK_WILD | TOK_DEEP, and the word
-// id of each level below TOK_LMAX (NONE for a word no filter uses), handed to a
-// sink level by level; k_match_fused keeps them in registers (WidsToRegs),
-// k_tokenize writes them to HBM (WidsToHbm).
+// id of each level below TOK_LMAX (NONE for a word no filter uses), which the
+// lane keeps in registers (WidsToRegs) for the walk that follows.
 constexpr int TOK_LMAX = 8;
-// k_match_fused: levels scanned, and dictionary slots in flight, at a time
-// (tokenize_grouped; k_tokenize's: GM_TOK_GROUP)
+// levels scanned, and dictionary slots in flight, at a time (tokenize_grouped)
 constexpr int TOK_GROUP = 3;
 constexpr uint32_t TOK_DOLLAR = 1u << 8, TOK_WILD = 1u << 9, TOK_DEEP = 1u << 10;
 
@@ -708,53 +699,10 @@ __device__ __forceinline__ WordTok next_word_s(const uint64_t* lds, uint32_t& po
   return w;
 }
 
-// Staged-text form of tokenize_topic (k_tokenize<1>): relative 32-bit positions, and the
-// level's wids[] slot advanced by n (no lev * n product per level).
-__device__ __forceinline__ uint32_t tokenize_staged(const uint64_t* lds, uint32_t pos, uint32_t end,
-                                                    const IndexView& ix, const uint8_t* tb_lo, uint64_t n,
-                                                    uint32_t* __restrict__ wp) {
-  uint32_t lev = 0, fl = 0;
-  WordTok w = next_word_s(lds, pos, end);
-  DictSlot d = dict_first(ix, w);
-  if (w.len > 0 && w.b0 == '$') fl |= TOK_DOLLAR;  // emqx_trie.erl:271-278
-  for (;;) {
-    if (w.len == 1 && (w.b0 == '+' || w.b0 == '#')) {  // emqx_topic:wildcard/1
-      fl |= TOK_WILD;
-      break;
-    }
-    const bool more = pos < end;
-    WordTok wn;
-    DictSlot dn;
-    if (more) {
-      ++pos;
-      wn = next_word_s(lds, pos, end);
-      dn = dict_first(ix, wn);
-    }
-    if (lev < TOK_LMAX) {
-      *wp = dict_resolve(ix, w, d, tb_lo);
-      wp += n;
-    }
-    ++lev;
-    if (!more) break;
-    w = wn;
-    d = dn;
-  }
-  if (lev > TOK_LMAX) fl |= TOK_DEEP;
-  return (lev < 255u ? lev : 255u) | fl;
-}
-
-// Where the word ids of one topic go: level-major HBM for k_walk (wids[level][topic],
-// a layout the walk reads coalesced), registers for the fused kernel.  Called for
-// levels 0, 1, 2, ... in order.
-template <bool NT>
-struct WidsToHbm {
-  uint32_t* wp;  // wids + t
-  uint64_t n;
-  __device__ __forceinline__ void operator()(uint32_t, uint32_t v) {
-    st_s<NT>(wp, v);
-    wp += n;
-  }
-};
+// Where the word ids of one topic go: the lane's registers.  Called for levels
+// 0, 1, 2, ... in order; the select chain keeps w[] out of scratch.  (The
+// tokenizers take it by reference: by value the kernel's registers are
+// allocated differently.)
 struct WidsToRegs {
   uint32_t (&w)[TOK_LMAX];
   __device__ __forceinline__ void operator()(uint32_t lev, uint32_t v) {
@@ -764,18 +712,19 @@ struct WidsToRegs {
   }
 };
 
-// Staged text, grouped: the words of G levels are scanned first and their
-// first dictionary slots loaded together, then resolved -- G L2 round trips in
-// flight per lane instead of tokenize_topic's one-ahead prefetch (the
-// tokenizer waits on the dictionary most of its time).  A word is kept as 4
+// Staged text, grouped: the words of TOK_GROUP levels are scanned first and
+// their first dictionary slots loaded together, then resolved -- TOK_GROUP L2
+// round trips in flight per lane instead of tokenize_topic's one-ahead prefetch
+// (the tokenizer waits on the dictionary most of its time).  A word is kept as 4
 // VGPRs (head, hash, start | len << 16; staged text is < 64 KiB) until it
 // resolves.  Levels past TOK_LMAX are only counted and checked for wildcards.
 // DBUF (the buffer form): the words' first dictionary slots are raw buffer
 // loads (32-bit offsets from ix.dict) that every lane issues; a lane without
 // a word at that level passes an out-of-range offset.
-template <int G, bool DBUF, class SINK>
+template <bool DBUF>
 __device__ __forceinline__ uint32_t tokenize_grouped(const uint64_t* lds, uint32_t pos, uint32_t end,
-                                                     const IndexView& ix, const uint8_t* tb_lo, SINK&& sink) {
+                                                     const IndexView& ix, const uint8_t* tb_lo, WidsToRegs&& sink) {
+  constexpr int G = TOK_GROUP;
   uint32_t lev = 0, fl = 0;
   bool more = true, wild = false;
   const TabRef<!DBUF> DT(ix.dict, uint32_t(ix.dict_mask + 1) * uint32_t(sizeof(DictSlot)));
@@ -843,9 +792,8 @@ __device__ __forceinline__ uint32_t tokenize_grouped(const uint64_t* lds, uint32
 // Unstaged text (a block whose text does not fit TOK_STAGE): one topic from
 // global memory, the next word's first dictionary slot loaded while this word
 // resolves.
-template <class SINK>
 __device__ __forceinline__ uint32_t tokenize_topic(ByteReader& rd, uint64_t pos, uint64_t end, const IndexView& ix,
-                                                   const uint8_t* tb, SINK&& sink) {
+                                                   const uint8_t* tb, WidsToRegs&& sink) {
   uint32_t lev = 0, fl = 0;
   WordTok w = next_word(rd, pos, end);
   DictSlot d = dict_first(ix, w);
@@ -878,193 +826,6 @@ __device__ __forceinline__ uint32_t tokenize_topic(ByteReader& rd, uint64_t pos,
 // scan their own topics from LDS instead of issuing dependent global loads
 // at every 8-byte boundary); a longer block reads global memory directly.
 constexpr int TOK_STAGE = 16384;
-
-// ---- split A/B forms (GM_MATCH_MAIN): k_tokenize + k_walk -------------------
-// The same work as two kernels: k_tokenize writes, per topic, its header and
-// the word id of each level below TOK_LMAX to HBM (hdr, wids[level][topic]);
-// k_walk reads them back.  DESIGN.md section 4 has their measurements.
-template <int G, bool NT>
-__global__ __launch_bounds__(256) void k_tokenize(const uint8_t* __restrict__ tb, const uint64_t* __restrict__ toff,
-                                                  uint64_t n, IndexView ix, uint32_t* __restrict__ hdr,
-                                                  uint32_t* __restrict__ wids, uint64_t t_base) {
-  __shared__ uint64_t s_txt[TOK_STAGE / 8 + 1];  // + one word of slack for the funnel shifts
-  const uint64_t t0 = t_base + uint64_t(blockIdx.x) * 256u;
-  const uint64_t t = t0 + threadIdx.x;
-  const uint64_t tl = t0 + 256 < n ? t0 + 256 : n;
-  const uint64_t lo = toff[t0] & ~7ull, hi = toff[tl];
-  const bool staged = hi - lo <= uint64_t(TOK_STAGE) - 8;  // block-uniform
-  if (staged) {
-    const uint64_t nw = ((hi - lo + 7) >> 3) + 1;  // topic buffers are padded by 64 bytes
-    for (uint64_t i = threadIdx.x; i < nw; i += 256) s_txt[i] = ld_s<NT>(reinterpret_cast<const uint64_t*>(tb + lo + 8 * i));
-  }
-  __syncthreads();
-  if (t >= n) return;
-  const uint64_t pos = toff[t], end = toff[t + 1];
-  uint32_t h;
-  if (staged) {
-    if constexpr (G == 1)
-      h = tokenize_staged(s_txt, uint32_t(pos - lo), uint32_t(end - lo), ix, tb + lo, n, wids + t);
-    else
-      h = tokenize_grouped<G, false>(s_txt, uint32_t(pos - lo), uint32_t(end - lo), ix, tb + lo, WidsToHbm<NT>{wids + t, n});
-  } else {
-    ByteReader rd{tb, ~0ull, 0};
-    h = tokenize_topic(rd, pos, end, ix, tb, WidsToHbm<NT>{wids + t, n});
-  }
-  st_s<NT>(hdr + t, h);
-}
-
-// k_walk: the NFA walk over pre-resolved word ids, a lane-private frontier in
-// registers.  Deep topics (more than TOK_LMAX levels) are queued for the
-// listed pass, which tokenizes for itself.
-#define GM_PUSH(idv, sigv)                                \
-  do {                                                    \
-    const uint32_t pid_ = (idv), psig_ = (sigv);          \
-    _Pragma("unroll") for (int q_ = 0; q_ < RFC; ++q_) {  \
-      if (nn == uint32_t(q_)) {                           \
-        nid[q_] = pid_;                                   \
-        nsig[q_] = psig_;                                 \
-      }                                                   \
-    }                                                     \
-    ++nn;                                                 \
-  } while (0)
-
-template <bool EXACT, int MINW>
-__global__ __launch_bounds__(256, MINW) void k_walk(const uint8_t* __restrict__ tb, const uint64_t* __restrict__ toff,
-                                                    uint64_t n, IndexView ix, const uint32_t* __restrict__ hdr,
-                                                    const uint32_t* __restrict__ wids, uint32_t* __restrict__ cnt,
-                                                    uint32_t* __restrict__ stage, uint32_t* __restrict__ ovf_list,
-                                                    uint32_t* __restrict__ ovf_n,
-                                                    unsigned long long* __restrict__ probe_tile,
-                                                    unsigned long long* __restrict__ wild_ctr,
-                                                    uint64_t* __restrict__ tsum, uint64_t t_base) {
-  constexpr int MC = FAST_MC;
-  const int lane = threadIdx.x & 63;
-  const uint64_t t = t_base + uint64_t(blockIdx.x) * 256u + threadIdx.x;
-  const uint64_t tile = t >> 6;
-  const bool valid = t < n;
-  uint32_t* const srow = stage + stage_index(tile, 0, lane);
-  constexpr uint32_t sstr = 64u;
-  uint32_t m_n = 0, probes = 0;
-  bool ovf = false, wild = false;
-
-  if (valid) {
-    const uint32_t h = hdr[t];
-    const uint32_t nlev = h & 0xFFu;
-    const bool dollar = (h & TOK_DOLLAR) != 0;
-    wild = (h & TOK_WILD) != 0;
-    if (h & TOK_DEEP) {
-      ovf = true;
-    } else if (wild) {
-      const uint64_t start = toff[t], end = toff[t + 1];
-      GM_WILD_ROW();
-    } else {
-      if (!dollar && ix.root_hash != NONE) GM_EMIT(ix.root_hash);  // '#' at the virtual root
-      uint32_t fid[RFC], fsig[RFC];
-#pragma unroll
-      for (int q = 0; q < RFC; ++q) fid[q] = fsig[q] = 0;
-      fid[0] = (!dollar && (ix.root_flags & HOT_PLUS)) ? FR_PLUS : 0u;
-      fsig[0] = ix.root_sig;
-      uint32_t cur_n = 1, nfinal = 0;
-      uint32_t wid_next = wids[t];
-      for (uint32_t level = 0; level < nlev && cur_n; ++level) {
-        const bool last = level + 1 == nlev;
-        const uint32_t wid = wid_next;
-        if (!last) wid_next = wids[uint64_t(level + 1) * n + t];  // prefetch
-        const uint32_t wbit = sig_bit(wid);
-        probes += 3 * cur_n;
-        uint32_t nid[RFC], nsig[RFC], nn = 0;
-#pragma unroll
-        for (int q = 0; q < RFC; ++q) nid[q] = nsig[q] = 0;
-        const uint32_t lvl = __builtin_amdgcn_readfirstlane(level);  // wave-uniform
-        const int ht = hot_table(lvl + 1);
-        const HotSlot* tab = ix.hot + ix.hot_off[ht];
-        const HotSlot* ptab = ix.hot + ix.hot_off[hot_table(lvl)];  // the frontier nodes' own table
-        const bool hflat = (ix.flags & IX_HOT_FLAT) != 0;
-        const bool hrh = ((ix.rh_mask >> ht) & 1u) != 0;  // Robin Hood ordered table
-        const uint64_t cap = ix.hot_cap[ht];
-        const uint32_t capu = uint32_t(cap);
-        const bool wok = wid != NONE;
-        // bit q: the exact probe of entry q can hit (signature, then the
-        // table's exact-edge filter when it has one: an L2 hit that saves a
-        // random line for most of the probes the signature lets through)
-        uint32_t xmask = 0;
-#pragma unroll
-        for (int q = 0; q < RFC; ++q)
-          if (uint32_t(q) < cur_n && wok && (fsig[q] & wbit)) xmask |= 1u << q;
-        const uint32_t fmask = ix.efilt_mask[ht];  // wave-uniform
-        if (fmask && xmask) {
-          const uint32_t* ft = ix.efilt + ix.efilt_off[ht];
-          uint32_t fw[RFC], fb[RFC];
-#pragma unroll
-          for (int q = 0; q < RFC; ++q) {
-            fw[q] = fb[q] = 0;
-            if (xmask & (1u << q)) {
-              const uint32_t fh = edge_filter_hash(hot_key(fid[q] & ID_MASK, wid, lvl));
-              fb[q] = edge_filter_bits(fh);
-              fw[q] = ft[edge_filter_word(fh, fmask)];
-            }
-          }
-#pragma unroll
-          for (int q = 0; q < RFC; ++q)
-            if ((fw[q] & fb[q]) != fb[q]) xmask &= ~(1u << q);
-        }
-#pragma unroll
-        for (int i = 0; i < RFC; ++i) {
-          if (uint32_t(i) < cur_n) {
-            const uint32_t ia = fid[i] & ID_MASK;
-            const bool ax = (xmask >> i) & 1u, ap = (fid[i] & FR_PLUS) != 0;
-            uint32_t sax = 0, sap = 0;
-            HotRec rax{}, rap{};
-            GM_PROBE_ISSUE(ax, ia, false, sax, rax);
-            GM_PROBE_ISSUE(ap, ia, true, sap, rap);
-            GM_PROBE_TAKE(ax, ia, false, sax, rax);
-            GM_PROBE_TAKE(ap, ia, true, sap, rap);
-          }
-        }
-        if (nn > RFC) {
-          ovf = true;
-          break;
-        }
-#pragma unroll
-        for (int q = 0; q < RFC; ++q) {
-          fid[q] = nid[q];
-          fsig[q] = nsig[q];
-        }
-        cur_n = nn;
-      }
-      if (!ovf) {
-        probes += 2 * nfinal + 1;
-        if (m_n > MC) ovf = true;
-      }
-    }
-    if (ovf) probes = 0;  // the listed pass walks this topic again and counts it
-  }
-
-  if (valid) {
-    cnt[t] = ovf ? OVF_BIT : m_n;
-    if (ovf) ovf_list[atomicAdd(ovf_n, 1u)] = uint32_t(t);
-  }
-  // per-tile probe count and match count (the CSR scan's input; rows the
-  // listed / slow passes finish add theirs there): plain stores into the
-  // tile's slots, not atomics on one address
-  uint32_t ptot, mtot;
-  wave_excl_scan(probes, ptot);
-  wave_excl_scan(valid && !ovf ? m_n : 0u, mtot);
-  const unsigned long long wb = __ballot(valid && wild);
-  if (lane == 0) {
-    if (tile * 64 < n) {  // waves wholly past n have no slot
-      probe_tile[tile] = ptot;
-      tsum[tile] = mtot;
-    }
-    if (wb) atomicAdd(wild_ctr, (unsigned long long)__popcll(wb));
-  }
-}
-#undef GM_PUSH
-#undef GM_PROBE_ISSUE
-#undef GM_PROBE_TAKE
-#undef GM_VISIT
-#undef GM_WILD_ROW
-#undef GM_EMIT
 
 // ---- the coop walk: the wave's frontier as one compacted work list ---------
 // A lane-private frontier per topic (as k_match_lds keeps one) costs a wave as
@@ -1784,7 +1545,7 @@ __global__ __launch_bounds__(256, 8) void k_match_fused(const uint8_t* __restric
   uint32_t h = 0;
   if (valid) {
     if (staged) {
-      h = tokenize_grouped<TOK_GROUP, !FLAT>(s_txt, uint32_t(pos - lo), uint32_t(end - lo), ix, tb + lo, WidsToRegs{w});
+      h = tokenize_grouped<!FLAT>(s_txt, uint32_t(pos - lo), uint32_t(end - lo), ix, tb + lo, WidsToRegs{w});
     } else {
       ByteReader rd{tb, ~0ull, 0};
       h = tokenize_topic(rd, pos, end, ix, tb, WidsToRegs{w});
@@ -2293,37 +2054,11 @@ float ev_ms(hipEvent_t a, hipEvent_t b) {
 
 namespace {
 
-// Main-pass kernel selection.  GM_MATCH_MAIN (A/B knob, read per call so tests
-// cover every kind): fused (k_match_fused: tokenizer into registers + the
-// compacted wave walk in one kernel, default), splitw8 (k_tokenize + k_walk,
-// lane-private register frontier, 8-wave register budget), split (budget left
-// to the compiler).
-enum MainKind { MAIN_SPLIT, MAIN_SPLITW8, MAIN_FUSED };
-MainKind main_kind() {
-  const char* e = knob("GM_MATCH_MAIN");
-  static const struct { const char* name; MainKind kind; } names[] = {
-      {"split", MAIN_SPLIT}, {"splitw8", MAIN_SPLITW8}, {"fused", MAIN_FUSED}};
-  if (e)
-    for (const auto& nk : names)
-      if (!strcmp(e, nk.name)) return nk.kind;
-  return MAIN_FUSED;
-}
-
 constexpr int LISTED_FC = 16;  // frontier capacity of the listed pass
 
-// Tokenizer group size.  GM_TOK_GROUP (A/B knob, read once): 1 = one-ahead
-// dictionary prefetch, 3 (default) / 5 = words scanned and their dictionary
-// slots loaded G at a time.  Measured at C2: 3.54 / 3.42 / 3.90 ms (G = 5
-// needs 80 VGPRs, 6 waves per SIMD).  Read per call, so tests cover all three.
-int tok_group() {
-  const char* e = knob("GM_TOK_GROUP");
-  const int v = e ? atoi(e) : 3;
-  return (v == 1 || v == 5) ? v : 3;
-}
-
 // Non-temporal stream accesses.  GM_NT (A/B knob, read per call): the topic
-// text, word ids, headers, staging and counts as nt loads / stores (default;
-// C2: 12.15 -> 12.03 ms for the split pair, 10.45 -> 10.24 ms fused), 0 = plain.
+// text, staging and counts as nt loads / stores (default; C2: 10.45 -> 10.24 ms),
+// 0 = plain.
 bool nt_streams() {
   const char* e = knob("GM_NT");
   return !e || atoi(e) != 0;
@@ -2381,22 +2116,6 @@ void launch_assemble(hipStream_t st, uint64_t nblk, const CmpBufs* cb, const uin
     hipLaunchKernelGGL(k_assemble, dim3(nblk), dim3(256), 0, st, cnt, n, toff, stage, row_off, ids, gmap, cap);
 }
 
-void launch_tokenize(hipStream_t st, uint64_t nblk, const uint8_t* tb, const uint64_t* to, uint64_t n,
-                     const IndexView& v, uint32_t* hdr, uint32_t* wids, uint64_t t_base) {
-  const bool nt = nt_streams();
-#define GM_TOK(G)                                                                                          \
-  do {                                                                                                     \
-    if (nt) hipLaunchKernelGGL((k_tokenize<G, true>), dim3(nblk), dim3(256), 0, st, tb, to, n, v, hdr, wids, t_base); \
-    else hipLaunchKernelGGL((k_tokenize<G, false>), dim3(nblk), dim3(256), 0, st, tb, to, n, v, hdr, wids, t_base); \
-  } while (0)
-  switch (tok_group()) {
-    case 1: GM_TOK(1); break;
-    case 5: GM_TOK(5); break;
-    default: GM_TOK(3);
-  }
-#undef GM_TOK
-}
-
 // The listed pass over the main pass's overflow queue (list1, its count n1 on the device)
 template <bool EXACT>
 void launch_listed(hipStream_t st, const IndexView& v, const uint8_t* tb, const uint64_t* to, uint64_t n, uint32_t* cnt,
@@ -2426,26 +2145,11 @@ void with_flag(bool b, F&& f) {
 template <bool EXACT>
 void launch_match(hipStream_t st, const IndexView& v, const uint8_t* tb, const uint64_t* to, uint64_t n,
                   uint32_t* cnt, uint32_t* stage, uint32_t* list1, uint32_t* n1, uint32_t* list2, uint32_t* n2,
-                  unsigned long long* probe_ctr, unsigned long long* wild_ctr, uint32_t* hdr, uint32_t* wids,
-                  unsigned long long* probe_tile, uint64_t* tsum, hipEvent_t before_main, hipEvent_t after_main,
-                  const CmpBufs* cb, bool* listed_deferred) {
+                  unsigned long long* probe_ctr, unsigned long long* wild_ctr, unsigned long long* probe_tile,
+                  uint64_t* tsum, hipEvent_t before_main, hipEvent_t after_main, const CmpBufs* cb,
+                  bool* listed_deferred) {
   const uint64_t nblk = (n + 255) / 256;
   *listed_deferred = false;
-  const MainKind kind = main_kind();
-  if (kind != MAIN_FUSED) {
-    // the split A/B forms: events recorded around the two launches (cb is null: no compact staging)
-    hipEventRecord(before_main, st);
-    launch_tokenize(st, nblk, tb, to, n, v, hdr, wids, 0);
-    auto walk = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(nblk), dim3(256), 0, st, tb, to, n, v, hdr, wids, cnt, stage, list1, n1, probe_tile,
-                         wild_ctr, tsum, uint64_t(0));
-    };
-    if (kind == MAIN_SPLIT) walk(k_walk<EXACT, 1>);
-    else walk(k_walk<EXACT, 8>);
-    hipEventRecord(after_main, st);
-    launch_listed<EXACT>(st, v, tb, to, n, cnt, stage, list1, n1, list2, n2, probe_ctr, wild_ctr, tsum, cb);
-    return;
-  }
 #ifdef GM_PHASE_STATS
   uint32_t* phase_rec = nullptr;
   if (n && hipStreamSynchronize(st) == hipSuccess && hipMalloc(&phase_rec, (n + 63) / 64 * 128) == hipSuccess) {
@@ -2563,7 +2267,7 @@ struct MatchCall {
   int ctr_slot = -1;             // the pass-counter block of the context's ring, or -1 (counters behind toff)
   const uint8_t* tb = nullptr;
   const uint64_t* to = nullptr;
-  PoolBuf d_tb_own, d_to_own, row_off, cnt, stage, list1, list2, tsum, toff, probe_tile, hdr, wids;
+  PoolBuf d_tb_own, d_to_own, row_off, cnt, stage, list1, list2, tsum, toff, probe_tile;
   PoolBuf c_tlen, c_lstage, c_lcnt, c_cnt8, scan_blk, ids;
   CmpBufs cmpb{};
   uint64_t* toff_p = nullptr;
@@ -2702,13 +2406,6 @@ int MatchCall::submit(const emqx_gm_index* index, const uint8_t* tb_in, const ui
   }
   probe_tile = PoolBuf(ctx->pool, n_tiles * 8 + 8);
   if (!probe_tile.p) return set_err(ctx, EMQX_GM_ENOMEM, "match: probe workspace");
-  // split forms: per-topic header and word ids [level][topic] (the fused kernel keeps them in registers)
-  const bool fused = main_kind() == MAIN_FUSED;
-  if (!fused) {
-    hdr = PoolBuf(ctx->pool, n * 4 + 16);
-    wids = PoolBuf(ctx->pool, uint64_t(TOK_LMAX) * n * 4 + 16);
-    if (!hdr.p || !wids.p) return set_err(ctx, EMQX_GM_ENOMEM, "match: word-id workspace");
-  }
   // counters: u32 n1 @0 (main-pass overflow), u32 n2 @4 (listed-pass
   // overflow), u64 probes @16, u64 wildcard topics @24
   uint32_t* n1 = reinterpret_cast<uint32_t*>(ctrs_p);
@@ -2719,7 +2416,7 @@ int MatchCall::submit(const emqx_gm_index* index, const uint8_t* tb_in, const ui
   // before the main pass can be queued, a launch ~6)
   if (zero_ctrs) hipLaunchKernelGGL(k_zero16, dim3(1), dim3(64), 0, st, reinterpret_cast<uint32_t*>(ctrs_p));
 
-  cmp = fused && stage_compact() && uint64_t(idx->view.n_filters) < (1ull << CMP_SHIFT);
+  cmp = stage_compact() && uint64_t(idx->view.n_filters) < (1ull << CMP_SHIFT);
   if (cmp) {
     const char* le = knob("GM_LISTED_CAP");  // (tests: listed rows past it go to the slow path)
     cmpb.lcap = std::min<uint64_t>(n, le ? strtoull(le, nullptr, 10) : (1u << 20));
@@ -2734,8 +2431,7 @@ int MatchCall::submit(const emqx_gm_index* index, const uint8_t* tb_in, const ui
     cmpb.lcnt = c_lcnt.as<uint32_t>();
   }
   // ev[0] / ev[1]: the main pass's start and end (also the call's start: total_device_ms);
-  // an untimed call of the fused pass launches it without them
-  if (!fused) timed = true;  // (the split forms record their events around the launches)
+  // an untimed call launches it without them
   hipEvent_t main_ev0 = ev[0], main_ev1 = ev[1];
   if (!timed) main_ev0 = main_ev1 = nullptr;
   // GM_D0=0 (A/B knob, read per call): level 0 probed like any other level
@@ -2749,14 +2445,12 @@ int MatchCall::submit(const emqx_gm_index* index, const uint8_t* tb_in, const ui
   if (knob("GM_HOT_FLAT")) vcall.flags |= IX_HOT_FLAT;  // (test knob, also read per call: the flat instantiation)
   if (exact)
     launch_match<true>(st, vcall, tb, to, n, cnt.as<uint32_t>(), stage.as<uint32_t>(), list1.as<uint32_t>(), n1,
-                       list2.as<uint32_t>(), n2, probe_ctr, wild_ctr, hdr.as<uint32_t>(), wids.as<uint32_t>(),
-                       probe_tile.as<unsigned long long>(), tsum.as<uint64_t>(), main_ev0, main_ev1,
-                       cmp ? &cmpb : nullptr, &listed_deferred);
+                       list2.as<uint32_t>(), n2, probe_ctr, wild_ctr, probe_tile.as<unsigned long long>(),
+                       tsum.as<uint64_t>(), main_ev0, main_ev1, cmp ? &cmpb : nullptr, &listed_deferred);
   else
     launch_match<false>(st, vcall, tb, to, n, cnt.as<uint32_t>(), stage.as<uint32_t>(), list1.as<uint32_t>(), n1,
-                        list2.as<uint32_t>(), n2, probe_ctr, wild_ctr, hdr.as<uint32_t>(), wids.as<uint32_t>(),
-                        probe_tile.as<unsigned long long>(), tsum.as<uint64_t>(), main_ev0, main_ev1,
-                        cmp ? &cmpb : nullptr, &listed_deferred);
+                        list2.as<uint32_t>(), n2, probe_ctr, wild_ctr, probe_tile.as<unsigned long long>(),
+                        tsum.as<uint64_t>(), main_ev0, main_ev1, cmp ? &cmpb : nullptr, &listed_deferred);
   GM_HIP(ctx, hipGetLastError());
 
   // Assembly stream: a large device-buffer call's scan and speculative
@@ -2766,7 +2460,7 @@ int MatchCall::submit(const emqx_gm_index* index, const uint8_t* tb_in, const ui
   // walk's tail.  (Its pass counters were zeroed on the context stream; the
   // assembly then zeroes no ring block for a later call.)
   hipStream_t sa = st;
-  if (asm_overlap && fused) {
+  if (asm_overlap) {
     if (!ctx->stream_asm && hipStreamCreateWithFlags(&ctx->stream_asm, hipStreamNonBlocking) != hipSuccess)
       ctx->stream_asm = nullptr;
     if (ctx->stream_asm) {

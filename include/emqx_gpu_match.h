@@ -60,8 +60,7 @@
  *     GM_MPH_NO_FILTERED, GM_CHAIN, GM_NO_CHAIN, GM_NO_EDGE_FILTER,
  *     GM_EFILT_ALL, GM_EFILT_DIV, GM_EFILT_MAX_KB, GM_DICT_MUL, GM_L1_BYPASS,
  *     GM_TRIE_RUNS, GM_MIRROR, GM_NO_MIRROR;
- *   walk and staging:   GM_MATCH_MAIN (the superseded split forms),
- *     GM_TOK_GROUP, GM_FUSED_PRIO, GM_HOT_POLICY, GM_NT, GM_D0,
+ *   walk and staging:   GM_FUSED_PRIO, GM_HOT_POLICY, GM_NT, GM_D0,
  *     GM_STAGE_COMPACT, GM_STAGE_SC1, GM_LISTED_CAP, GM_LISTED_DEFER,
  *     GM_SCAN_SPLIT, GM_SCAN_SUMS, GM_NO_SPEC_IDS, GM_ASM_STREAM, GM_HOT_FLAT
  *     (per call too: the walk's flat-load instantiation);

@@ -16,7 +16,7 @@ f = glob.glob(f"gpurun_out/mem/p_{m}/**/*counter_collection.csv", recursive=True
 acc = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.Counter()
 for r in csv.DictReader(open(f)):
     k = r["Kernel_Name"].split("(")[0]
-    if "k_walk" not in k and "k_tokenize" not in k: continue
+    if "k_match" not in k: continue
     acc[k][r["Counter_Name"]] += float(r["Counter_Value"])
     n[(k, r["Counter_Name"])] += 1
 for k, d in acc.items():

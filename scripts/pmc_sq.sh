@@ -15,7 +15,7 @@ f = glob.glob(f"gpurun_out/pmc/{tag}/**/*counter_collection.csv", recursive=True
 acc = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.Counter()
 for r in csv.DictReader(open(f)):
     k = r["Kernel_Name"].split("(")[0]
-    if not any(x in k for x in ("k_walk", "k_tokenize", "k_assemble")): continue
+    if not any(x in k for x in ("k_match", "k_assemble")): continue
     acc[k][r["Counter_Name"]] += float(r["Counter_Value"]); n[(k, r["Counter_Name"])] += 1
 for k, d in acc.items():
     w = d.get("SQ_WAVES", 0) / max(1, n[(k, "SQ_WAVES")])

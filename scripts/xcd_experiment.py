@@ -1,4 +1,4 @@
-"""Experiment: does routing topics to XCDs by their level-1 word cut k_walk time?
+"""Experiment: does routing topics to XCDs by their level-1 word cut the main pass's time?
 Reorders a C2 batch on the host (bucket = hash(level-1 word) % 8) so that
 workgroup i (dispatched to XCD i % 8) sees only bucket i % 8, and compares the
 match-kernel time with the original order and with a bucket-sorted order whose

@@ -584,16 +584,12 @@ def test_tokenizer_alignments_and_bytes(ctx, orc):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("group", ["1", "3", "5"])
-def test_tokenizer_groups(ctx, orc, monkeypatch, group):
-    """k_tokenize<G> (GM_TOK_GROUP, words resolved G levels at a time): the
-    group boundary against wildcard words, '$' first words, empty levels,
-    trailing '/', and topics deeper than the 8 tokenized levels must give
-    the same rows as the oracle for every G.  k_tokenize runs only under the
-    split main passes (the default fused kernel tokenizes into registers, always
-    three levels at a time), so every G is run under GM_MATCH_MAIN=splitw8
-    (k_walk), and under the default as before."""
-    monkeypatch.setenv("GM_TOK_GROUP", group)
+def test_tokenizer_group_and_depth_boundaries(ctx, orc):
+    """k_match_fused's tokenizer resolves a topic's words into registers three
+    levels at a time, eight levels at the most: wildcard words, '$' first
+    words, empty levels and a trailing '/' on either side of a group boundary,
+    and topics deeper than the 8 tokenized levels (finished by the listed
+    pass), must give the same rows as the oracle."""
     rng = random.Random(23)
     words = [b"a", b"b", b"", b"cc", b"longword_over_8_bytes", b"$SYS", b"d"]
     filters = {b"#", b"+", b"+/+", b"a/#", b"$SYS/#", b"+/b/#", b"a/b/cc", b"/#", b"a//cc", b"a/b/"}
@@ -610,11 +606,8 @@ def test_tokenizer_groups(ctx, orc, monkeypatch, group):
         if rng.random() < 0.1:  # a wildcard word at any level, including past the group / 8-level bounds
             lev[rng.randrange(n)] = rng.choice([b"+", b"#"])
         topics.append(b"/".join(lev))
-    for main in (None, "splitw8"):
-        if main:
-            monkeypatch.setenv("GM_MATCH_MAIN", main)
-        _check(ctx, orc, sorted(filters), topics, True)
-        _check(ctx, orc, filters, topics, False)
+    _check(ctx, orc, sorted(filters), topics, True)
+    _check(ctx, orc, filters, topics, False)
 
 
 @pytest.mark.gpu

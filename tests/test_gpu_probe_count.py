@@ -13,8 +13,7 @@ The contract (include/emqx_gpu_match.h): exact when no row leaves a pass for
 capacity; otherwise each such row may be counted by up to two passes.  The
 batches of the equality tests are built so that no row does -- at most 8
 matches per row (FAST_MC = 16) and a frontier of at most 3 per topic (64 x 3 <
-CW_CAP, <= RFC of the split walks) -- which each test checks on the CPU with
-the reference.  test_overflow_rows_* assert the bounds for rows that do.
+CW_CAP) -- which each test checks on the CPU with the reference.  test_overflow_rows_* assert the bounds for rows that do.
 """
 
 import itertools
@@ -264,9 +263,6 @@ def test_chain_nodes_every_length(ctx, orc, chain, form, monkeypatch):
 # ------------------------------------------------------------------ kernel forms
 KERNEL_FORMS = [{}, {"GM_STAGE_COMPACT": "0"}, {"GM_D0": "0"}, {"GM_STAGE_SC1": "1"}, {"GM_HOT_FLAT": "1"},
                 {"GM_FUSED_PRIO": "0"}, {"GM_NT": "0"}, {"GM_NT": "0", "GM_STAGE_COMPACT": "0"}]
-KERNEL_FORMS += [{"GM_MATCH_MAIN": m, "GM_TOK_GROUP": g} for m in ("split", "splitw8")
-                 for g in ("1", "3", "5")]
-KERNEL_FORMS += [{"GM_MATCH_MAIN": "splitw8", "GM_NT": "0"}]
 
 
 def _form_id(env):
@@ -276,9 +272,9 @@ def _form_id(env):
 @pytest.mark.parametrize("env", KERNEL_FORMS, ids=_form_id)
 @pytest.mark.parametrize("chains", [False, True], ids=["plain", "chains"])
 def test_kernel_forms(ctx, orc, base, env, chains, monkeypatch):
-    """Every main-pass kernel and instantiation: k_match_fused with each A/B
-    form, k_tokenize<1|3|5> + k_walk<1|8>, nt and plain
-    streams; rows against the oracle and the counters against the reference."""
+    """Every instantiation of the main pass: k_match_fused with each A/B form,
+    nt and plain streams; rows against the oracle and the counters against the
+    reference."""
     if chains:
         monkeypatch.setenv("GM_CHAIN", "1")
     idx = ctx.build_index(base.filters)
@@ -439,7 +435,7 @@ def _overflow_case():
     return ref, tiles, set(heavy) | {NARROW}
 
 
-@pytest.mark.parametrize("main", ["fused", "fused_columns", "splitw8"])
+@pytest.mark.parametrize("main", ["fused", "fused_columns"])
 def test_overflow_rows_bounds_and_slow_count(ctx, orc, main, monkeypatch):
     """Tiles of light topics beside tiles of topics with more than 16 matches
     (past FAST_MC: the main and the listed pass give them up, the slow path
@@ -450,15 +446,14 @@ def test_overflow_rows_bounds_and_slow_count(ctx, orc, main, monkeypatch):
     -- and n_overflow is the rows the slow path completed: the heavy ones.
 
     Measured on an MI355X, this batch (613 topics, sum P(light) = 6,760, sum
-    P(heavy) = 54,264): probes = 55,865 with the fused main pass,
-    37,477 with k_walk, which zeroes the count of a topic it gives up (the
-    18,388 between them are what coop_walk_tile keeps of the heavy rows; it
-    accumulates per entry lane and cannot take a topic's count back).  Both
-    are under sum P = 61,024: these wide rows are cut short in both passes."""
+    P(heavy) = 54,264): probes = 55,865 with the fused main pass.  (The
+    since-removed split walk, which zeroed the count of a topic it gave up,
+    measured 37,477; the 18,388 between them are what coop_walk_tile keeps of
+    the heavy rows: it accumulates per entry lane and cannot take a topic's
+    count back.)  That is under sum P = 61,024: these wide rows are cut short
+    in both passes."""
     if main == "fused_columns":
         monkeypatch.setenv("GM_STAGE_COMPACT", "0")
-    elif main != "fused":
-        monkeypatch.setenv("GM_MATCH_MAIN", main)
     ref, tiles, heavy = _overflow_case()
     topics = [t for tile in tiles for t in tile]
     idx = ctx.build_index(ref.filters)
@@ -478,16 +473,14 @@ def test_overflow_rows_bounds_and_slow_count(ctx, orc, main, monkeypatch):
     idx.release()
 
 
-@pytest.mark.parametrize("main", ["fused", "splitw8"])
-def test_overflow_narrow_rows_counted_by_up_to_two_passes(ctx, orc, main, monkeypatch):
+@pytest.mark.parametrize("main", ["fused"])
+def test_overflow_narrow_rows_counted_by_up_to_two_passes(ctx, orc, main):
     """The upper bound is reached: a topic with 17 matches and a frontier of 2
     is walked to its end by the main pass and again by the listed pass before
     the slow path finishes it.  Measured on an MI355X: sum P(light) = 2,679, sum
     P(heavy) = 3,478; the fused main pass gives probes = 9,635 = 2,679 + 2 x
-    3,478 (more than sum P = 6,157), k_walk 6,157 (the listed pass alone
-    counts a topic k_walk gives up)."""
-    if main != "fused":
-        monkeypatch.setenv("GM_MATCH_MAIN", main)
+    3,478 (more than sum P = 6,157).  (The since-removed split walk gave
+    6,157: the listed pass alone counted a topic that walk gave up.)"""
     ref, tiles, heavy = _overflow_case()
     topics = tiles[0] + [NARROW] * 64 + tiles[2] + [NARROW] * 10
     idx = ctx.build_index(ref.filters)
