@@ -14,11 +14,13 @@ from .shared import SharedSub, SharedTable  # noqa: F401
 from .authz import Authz, AuthzTable  # noqa: F401
 from .cluster import ClusterRoutes, DestTable, ForwardPlan, build_dests  # noqa: F401
 from .subopts import SubOptTable, build_subopts, pack_msg, pack_opt, unpack_dopt  # noqa: F401
+from .batches import DeviceBatches, SessionBatches  # noqa: F401
 from . import topic  # noqa: F401
 
 __all__ = ["Context", "Index", "DeviceCsr", "Trie", "Router", "SessionRouter", "Broker", "TopicRuleIndex", "topic",
            "RetainedIndex", "Retainer", "SharedTable", "SharedSub", "Authz", "AuthzTable",
            "ClusterRoutes", "DestTable", "ForwardPlan", "build_dests",
            "SubOptTable", "build_subopts", "pack_opt", "pack_msg", "unpack_dopt",
+           "SessionBatches", "DeviceBatches",
            "GpuMatchError",
            "pack", "gen_filter_codes", "render_codes", "default_context"]

@@ -26,6 +26,7 @@ DESTS_SKIP_UNKNOWN = 0x1
 SO_SKIP_UNKNOWN = 0x1
 SO_NO_PUBLISHER = 0xFFFFFFFF
 SO_FLAG, SO_DROP = 0, 1
+SO_LEAD = 2  # emqx_gm_deliver_batches only
 OPEN_MIRROR_EAGER = 0x1
 OPEN_MIRROR_LAZY = 0x2
 IMAGE_NO_BLOB = 0x1
@@ -117,6 +118,13 @@ class SubOptsInfo(C.Structure):
 class Deliveries(C.Structure):
     _fields_ = [("deliveries", Csr), ("dopt", C.POINTER(C.c_uint8)), ("row_dropped", C.POINTER(C.c_uint32)),
                 ("n_dropped", C.c_uint64)]
+
+
+class Batches(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_deliveries", C.c_uint64), ("n_batches", C.c_uint64),
+                ("n_dropped", C.c_uint64), ("subs", C.POINTER(C.c_uint32)), ("batch_off", C.POINTER(C.c_uint64)),
+                ("rows", C.POINTER(C.c_uint32)), ("filters", C.POINTER(C.c_uint32)), ("dopt", C.POINTER(C.c_uint8)),
+                ("batch_dropped", C.POINTER(C.c_uint32)), ("on_device", C.c_int32), ("priv", C.c_void_p)]
 
 
 class PublishOpts(C.Structure):
@@ -255,6 +263,8 @@ SIGNATURES = {
     "emqx_gm_subopts_index": (_vp, [_vp]),
     "emqx_gm_deliveries_free": (_i32, [_vp, C.POINTER(Deliveries)]),
     "emqx_gm_subopts_info": (_i32, [_vp, C.POINTER(SubOptsInfo)]),
+    "emqx_gm_deliver_batches": (_i32, [_vp, _vp, C.POINTER(Csr), _vp, _vp, _u32, C.POINTER(Batches)]),
+    "emqx_gm_batches_free": (_i32, [_vp, C.POINTER(Batches)]),
     "emqx_gm_subopts_release": (_i32, [_vp]),
     "emqx_gm_publish_window": (_i32, [_vp, _vp, _vp, _vp, _u64, C.POINTER(PublishOpts), C.POINTER(PublishResult),
                                       C.POINTER(PublishStats)]),
@@ -308,6 +318,10 @@ SIGNATURES = {
     "emqx_gm_deliver_host": (_i32, [_vp, C.POINTER(Csr), _vp, _vp, _u32, C.POINTER(Deliveries)]),
     "emqx_gm_deliveries_free_host": (_i32, [C.POINTER(Deliveries)]),
     "emqx_gm_subopts_last_times": (_i32, [_vp, C.POINTER(C.c_double)]),
+    "emqx_gm_deliver_batches_host": (_i32, [_vp, C.POINTER(Csr), _vp, _vp, _u32, C.POINTER(Batches)]),
+    "emqx_gm_batches_free_host": (_i32, [C.POINTER(Batches)]),
+    "emqx_gm_deliver_batches_chunked": (_i32, [_vp, _vp, C.POINTER(Csr), _vp, _vp, _u32, _u32, C.POINTER(Batches)]),
+    "emqx_gm_batches_last_times": (_i32, [_vp, C.POINTER(C.c_double)]),
     "emqx_gm_authz_compile_host": (_i32, [C.POINTER(AuthzDesc), C.POINTER(_vp)]),
     "emqx_gm_authz_check_host": (_i32, [_vp, C.POINTER(AuthzBatch), _vp, _vp]),
     "emqx_gm_authz_last_kernel_ms": (_i32, [_vp, C.POINTER(C.c_double)]),

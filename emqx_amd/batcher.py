@@ -78,6 +78,19 @@ class _IdsOpts:
         return self.ids.tolist()
 
 
+class _Counted:
+    """A filter's segment of a window whose local deliveries went out by session
+    batch (``PublishBatcher(batches=True)``): the subscribers the snapshot lists
+    for it, the deliveries the mode kept, and those a ``deliver_batch`` took."""
+    __slots__ = ("listed", "kept", "n")
+
+    def __init__(self, listed, kept, n):
+        self.listed, self.kept, self.n = listed, kept, n
+
+    def __len__(self):
+        return self.listed
+
+
 def msg_meta(topic, msg):
     """The default ``PublishBatcher(msg_meta=)``: (qos, retain, from[, headers.retained])
     of a message given as a dict with those keys; anything else is (0, False, None)."""
@@ -252,6 +265,32 @@ class GpuRoutes:
         d = tab.deliver((ro, ids), msg_flags, msg_from, False, index=idx)
         return self._cut_opts(idx, ro, ids, d, drop)
 
+    def groups_batches(self, topics: Sequence[bytes], msg_flags, msg_from, mode: str = "flag"):
+        """The window's session batches next to its groups: one match, one
+        emqx_gm_deliver_batches on its rows.  Returns (rows, names, batches):
+        rows[k] = [(filter, filter id, subscribers listed)] per matched filter of
+        topic k, names = {filter id: filter}, batches the ``SessionBatches`` --
+        per subscriber id its (row, filter id, byte) entries in window order.
+        ``mode``: "flag", "drop" or "lead" (the reference's dropwhile)."""
+        self.subopts_on = True
+        self.refresh()
+        if self.stale:
+            raise RuntimeError("stale_index")
+        idx, tab = self.index, self._so_table
+        ro, ids = self.ctx.match(idx, list(topics), exact=True)
+        sb = tab.deliver_batches((ro, ids), msg_flags, msg_from, mode, index=idx)
+        rows, names = [], {}
+        for k in range(len(ro) - 1):
+            row = []
+            for f in ids[ro[k]:ro[k + 1]].tolist():
+                name = self._names.get(f)
+                if name is None:
+                    name = self._names[f] = idx.filter(f)
+                names[f] = name
+                row.append((name, f, idx.subscriber_count(f)))
+            rows.append(row)
+        return rows, names, sb
+
     def _cut_opts(self, idx, ro, ids, d, drop: bool) -> List[Row]:
         """FLAG-mode deliveries (a ``Delivered``) cut into one (filter, _IdsOpts) per matched filter."""
         out = []
@@ -395,7 +434,19 @@ class PublishBatcher:
     (bit 4) and counts them in ``metrics['delivery.dropped.no_local']``;
     otherwise the bit goes to ``deliver`` and the session drops what
     ignore_local/4 would.  Without
-    ``subopts`` nothing changes."""
+    ``subopts`` nothing changes.
+
+    ``batches`` (needs ``subopts`` and ``deliver_batch``; not with ``one_call``,
+    ``shared`` or ``cluster`` for now): the window's local deliveries go out by
+    SUBSCRIBER -- ``routes.groups_batches`` (one match, one
+    emqx_gm_deliver_batches) and ONE ``deliver_batch(sub, [(filter, msg, byte),
+    ...]) -> bool`` per subscriber per window, its deliveries in window order:
+    the list emqx_channel:handle_deliver/2 gets from a drained mailbox.
+    ``drop_no_local`` then selects the reference's own rule (EMQX_GM_SO_LEAD:
+    only the leading run of hits of a batch is removed, bit 4 cleared) and
+    ``metrics['delivery.dropped.no_local']`` counts what it removed
+    (``batch_dropped``).  A subscriber whose batch was emptied gets no call.
+    Without ``batches`` nothing changes."""
 
     def __init__(self, groups_fn: Optional[Callable[[Sequence[bytes]], List[Row]]] = None, max_batch: int = 4096,
                  window_s: float = 0.001, subscribers: Optional[Dict[int, object]] = None,
@@ -412,7 +463,8 @@ class PublishBatcher:
                  shared_hash: Optional[Callable[[bytes, object], int]] = None, cluster=None,
                  forward_batch: Optional[Callable[[bytes, List[Tuple[bytes, object]]], object]] = None,
                  one_call: bool = False, subopts: bool = False, drop_no_local: bool = False,
-                 msg_meta: Callable[[bytes, object], tuple] = msg_meta):
+                 msg_meta: Callable[[bytes, object], tuple] = msg_meta, batches: bool = False,
+                 deliver_batch: Optional[Callable[[object, List[Tuple[bytes, object, int]]], bool]] = None):
         if routes is None and isinstance(getattr(groups_fn, "__self__", None), GpuRoutes):
             routes = groups_fn.__self__
         if groups_fn is None:
@@ -434,7 +486,12 @@ class PublishBatcher:
             raise TypeError("PublishBatcher(subopts=True) needs routes")
         if subopts and not one_call and (shared is not None or cluster is not None):
             raise TypeError("PublishBatcher(subopts=True) with shared / cluster needs one_call=True (the window call)")
+        if batches and one_call:
+            raise TypeError("PublishBatcher(batches=True) with one_call is not supported yet")
+        if batches and (not subopts or deliver_batch is None):
+            raise TypeError("PublishBatcher(batches=True) needs subopts=True and deliver_batch")
         self.subopts, self.drop_no_local, self.msg_meta = subopts, drop_no_local, msg_meta
+        self.by_batch, self.deliver_batch = batches, deliver_batch
         self.one_call = one_call
         self.routes, self.shared, self.shared_strategy = routes, shared, shared_strategy
         self.cluster = cluster
@@ -565,6 +622,12 @@ class PublishBatcher:
                 if self.cluster is None:
                     return [("ok", r, p) for r, p in zip(rows, picks)]
                 return [("ok", r, p, w) for r, p, w in zip(rows, picks, self._forward_window(idx, csr, msgs, plan))]
+            if self.by_batch:  # the window's local deliveries by subscriber: one match, one batches call
+                msgs = msgs if msgs is not None else [None] * len(topics)
+                flags, froms = self._msg_opts(topics, msgs)
+                rows, names, sb = self.routes.groups_batches(list(topics), flags, froms,
+                                                             "lead" if self.drop_no_local else "flag")
+                return [("ok", r) for r in self._deliver_batches(rows, names, sb, msgs)]
             if self.subopts:  # the window's deliveries with their option bytes: one match, one deliver call
                 msgs = msgs if msgs is not None else [None] * len(topics)
                 flags, froms = self._msg_opts(topics, msgs)
@@ -572,6 +635,29 @@ class PublishBatcher:
             return [("ok", r) for r in self.groups_fn(list(topics))]
         except Exception as e:  # the NIF's {error, _}: every caller takes the reference path
             return [("error", str(e))] * len(topics)
+
+    def _deliver_batches(self, rows, names, sb, msgs) -> List[Row]:
+        """One ``deliver_batch`` per subscriber of the window (handle_deliver/2's
+        list); per row, [(filter, _Counted)] for ``route_row``'s bookkeeping.
+        The counts are kept per (row, filter id): a matched row lists a filter
+        once (the match's rows are sets), so a segment is one key."""
+        kept: Dict[Tuple[int, int], int] = {}
+        took: Dict[Tuple[int, int], int] = {}
+        for sid, rws, fls, bts in sb.batches():
+            keys = list(zip(rws.tolist(), fls.tolist()))
+            for k in keys:
+                kept[k] = kept.get(k, 0) + 1
+            sub = self.subscribers.get(int(sid))
+            if sub is None or not keys:
+                continue
+            if self.deliver_batch(sub, [(names[f], msgs[r], b) for (r, f), b in zip(keys, bts.tolist())]):
+                for k in keys:
+                    took[k] = took.get(k, 0) + 1
+        if sb.batch_dropped is not None:
+            with self._mlock:
+                self.metrics["delivery.dropped.no_local"] += int(sb.batch_dropped.sum())
+        return [[(name, _Counted(listed, kept.get((k, f), 0), took.get((k, f), 0))) for name, f, listed in row]
+                for k, row in enumerate(rows)]
 
     def _forward_window(self, idx, csr, msgs, plan=None):
         """The window's remote node routes: one plan call (or the window call's
@@ -693,6 +779,11 @@ class PublishBatcher:
     def dispatch_ids(self, f: bytes, ids, topic: bytes, msg):
         """do_dispatch/2,3: one delivery per live subscriber; none live is a drop."""
         n = 0
+        if isinstance(ids, _Counted):  # already delivered with its window's session batches
+            if ids.n or ids.kept < ids.listed:  # (removed as no_local in its session: not a no_subscribers drop)
+                return ("ok", ids.n)
+            self.dropped(topic, msg)
+            return ("error", "no_subscribers")
         if isinstance(ids, _IdsOpts):  # the option byte goes with the id: deliver(sub, filter, msg, byte)
             for sid, b in zip(ids.ids.tolist(), ids.dopt.tolist()):
                 sub = self.subscribers.get(int(sid))

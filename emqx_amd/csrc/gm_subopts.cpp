@@ -175,6 +175,7 @@ int so_compile(const SoInput& in, uint64_t n_filters, const uint64_t* sub_off, c
                   n_subs,
                   n_nl,
                   uint32_t(n_filters)};
+  for (uint64_t k = 0; k < n_subs; ++k) so->max_sub = std::max(so->max_sub, sub_ids[k]);
   so->dv = so->hv;  // (so_upload rebases the table's pointers and takes the lists from the snapshot)
   so->info.n_entries = stored;
   so->info.n_defaulted = defaulted;
@@ -186,8 +187,8 @@ int so_compile(const SoInput& in, uint64_t n_filters, const uint64_t* sub_off, c
 }
 
 int so_check_call(const emqx_gm_subopts* so, const emqx_gm_csr* m, const uint8_t* msg_flags, const uint32_t* msg_from,
-                  uint32_t mode, std::string* why) {
-  if (mode != EMQX_GM_SO_FLAG && mode != EMQX_GM_SO_DROP) {
+                  uint32_t mode, std::string* why, bool lead_ok) {
+  if (mode != EMQX_GM_SO_FLAG && mode != EMQX_GM_SO_DROP && !(lead_ok && mode == EMQX_GM_SO_LEAD)) {
     *why = "mode";
     return EMQX_GM_EINVAL;
   }

@@ -97,9 +97,13 @@ struct emqx_gm_subopts {
   size_t bytes = 0;              // ... its bytes (the head of blob)
   gm::HostBytes blob;            // host copy: the device arrays, then sub_off and sub_ids
   gm::SoView hv{}, dv{};
+  uint32_t max_sub = 0;          // the lists' largest subscriber id (gm_batches.hip: its 8-bit digits are the radix passes)
   emqx_gm_subopts_info_t info{};
   std::mutex mu;                 // guards last_ms
   double last_ms[3] = {0, 0, 0};  // lengths + scan + row offsets, copy, total
+  // a batches call: count, expand, partition, heads..emit, total (ms; of the last call that had deliveries); its
+  // passes; the host-blocking waits of the last call
+  double sb_ms[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
 namespace gm {
@@ -118,8 +122,9 @@ int so_compile(const SoInput& in, uint64_t n_filters, const uint64_t* sub_off, c
                const std::function<bool(const uint8_t*, uint64_t, uint32_t*)>& resolve, emqx_gm_subopts** out,
                std::string* why);
 // every check of a deliver call's inputs that needs no device
+// lead_ok: EMQX_GM_SO_LEAD is a mode of this call (emqx_gm_deliver_batches alone)
 int so_check_call(const emqx_gm_subopts* so, const emqx_gm_csr* m, const uint8_t* msg_flags, const uint32_t* msg_from,
-                  uint32_t mode, std::string* why);
+                  uint32_t mode, std::string* why, bool lead_ok = false);
 int so_deliver_host(const emqx_gm_subopts* so, const emqx_gm_csr* m, const uint8_t* msg_flags,
                     const uint32_t* msg_from, uint32_t mode, emqx_gm_deliveries* out);
 // gm_subopts.hip (device)
@@ -156,6 +161,10 @@ struct SoSpec {
 };
 int so_queue_spec(emqx_gm_ctx* ctx, emqx_gm_subopts* so, const uint64_t* d_ro, const uint32_t* d_ids, uint64_t n,
                   uint64_t cap, uint64_t cap_d, uint32_t mode, const void* msgs, SoSpec* out);
+// k_so_seglen over nnz entries in FLAG form (the lengths, the hits) on stream st: gm_batches.hip counts a
+// window's deliveries with the same kernel
+int so_launch_seglen(hipStream_t st, const SoView& dv, const uint64_t* d_mro, uint64_t n_rows, const uint32_t* d_mids,
+                     uint64_t nnz, const uint32_t* d_from, uint64_t* seg_len, uint32_t* seg_hit);
 int so_queue_pack(emqx_gm_ctx* ctx, const SoSpec& run, uint64_t n, uint64_t cap_d, uint64_t* o_ro, uint32_t* o_ids,
                   uint8_t* o_opt, uint32_t* o_rd, uint64_t* o_meta);
 }  // namespace gm

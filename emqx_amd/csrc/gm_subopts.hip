@@ -294,6 +294,14 @@ struct SoUndo {  // a failing call hands back no buffers
 
 }  // namespace
 
+// (gm_batches.hip counts a window's deliveries with the same kernel)
+int so_launch_seglen(hipStream_t st, const SoView& dv, const uint64_t* d_mro, uint64_t n_rows, const uint32_t* d_mids,
+                     uint64_t nnz, const uint32_t* d_from, uint64_t* seg_len, uint32_t* seg_hit) {
+  hipLaunchKernelGGL(k_so_seglen, dim3(blocks_of(nnz)), dim3(256), 0, st, dv, d_mro, n_rows, d_mids, nnz,
+                     static_cast<const uint64_t*>(nullptr), d_from, false, seg_len, seg_hit);
+  return hipGetLastError() == hipSuccess ? 0 : EMQX_GM_EDEVICE;
+}
+
 int so_upload(emqx_gm_ctx* ctx, emqx_gm_subopts* so) {
   if (const int rc = table_upload(ctx, so->blob, so->bytes, "subopts_build", &so->dev_base)) return rc;
   const void* hb = so->blob.data();

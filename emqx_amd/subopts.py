@@ -256,3 +256,13 @@ def build_subopts(ctx, index, entries: Iterable, default: int = 0, skip_unknown:
     check(lib().emqx_gm_subopts_build(ctx.h, index.h, _ptr(fb), _ptr(fo), _ptr(es), _ptr(eo), ne, _opt_byte(default),
                                       _lib.SO_SKIP_UNKNOWN if skip_unknown else 0, C.byref(h)), ctx.h, "subopts_build")
     return SubOptTable(ctx, h, index)
+
+
+# session batches (emqx_gm_deliver_batches): the same deliveries grouped by subscriber, emqx_amd/batches.py
+from . import batches as _batches  # noqa: E402
+from .batches import DeviceBatches, SessionBatches  # noqa: E402,F401
+
+SubOptTable.deliver_batches = _batches.deliver_batches
+SubOptTable.deliver_batches_device = _batches.deliver_batches_device
+SubOptTable.deliver_batches_host = _batches.deliver_batches_host
+SubOptTable.batches_last_times = _batches.batches_last_times

@@ -207,6 +207,25 @@ int emqx_gm_deliver_host(const emqx_gm_subopts *so, const emqx_gm_csr *matches, 
                          const uint32_t *msg_from, uint32_t mode, emqx_gm_deliveries *out);
 int emqx_gm_deliveries_free_host(emqx_gm_deliveries *d);
 int emqx_gm_subopts_last_times(const emqx_gm_subopts *so, double *ms3);
+/* Session batches (emqx_gm_deliver_batches).  batches_host: the plain
+ * single-threaded walk over the table's host copy (host rows; any table; no
+ * device): dispatch in window order into per-subscriber lists, then the
+ * mode's removal.  Its arrays are malloc'd (free with emqx_gm_batches_free and
+ * a NULL ctx, or, in a build without the device half,
+ * emqx_gm_batches_free_host).  batches_chunked: the device call with the radix
+ * partition's chunk count forced (0: the library's rule; clamped to one chunk
+ * per 256 deliveries; more than 1024: EMQX_GM_EINVAL).  batches_last_times:
+ * device ms of the last call's count, expand, partition (all passes) and
+ * heads + removal + emit steps, the whole call on the stream, the number of
+ * radix passes (all six of the last call that had deliveries), and ms7[6]: the
+ * host-blocking waits the last call made. */
+int emqx_gm_deliver_batches_host(const emqx_gm_subopts *so, const emqx_gm_csr *matches, const uint8_t *msg_flags,
+                                 const uint32_t *msg_from, uint32_t mode, emqx_gm_batches *out);
+int emqx_gm_batches_free_host(emqx_gm_batches *b);
+int emqx_gm_deliver_batches_chunked(emqx_gm_ctx *ctx, emqx_gm_subopts *so, const emqx_gm_csr *matches,
+                                    const uint8_t *msg_flags, const uint32_t *msg_from, uint32_t mode,
+                                    uint32_t n_chunks, emqx_gm_batches *out);
+int emqx_gm_batches_last_times(const emqx_gm_subopts *so, double *ms7);
 
 /* Test and measurement support for the authorization table (no product path
  * uses these).  compile_host: the table compiled on the host alone (no device,

@@ -815,8 +815,10 @@ int emqx_gm_dests_release(emqx_gm_dests *dt);
  * the No-Local hit (EMQX_GM_SO_FLAG only).
  * NO LOCAL: the reference applies lists:dropwhile over whatever batch a channel
  * drained from its mailbox (emqx_session.erl:281): it drops only the LEADING
- * run of hits.  Batch boundaries are mailbox timing no window can know, so the
- * library evaluates the predicate per delivery.  EMQX_GM_SO_FLAG removes
+ * run of hits.  Batch boundaries are mailbox timing no window can know, so
+ * emqx_gm_deliver evaluates the predicate per delivery (emqx_gm_deliver_batches
+ * below delivers the window as ONE batch per subscriber and applies dropwhile
+ * itself: EMQX_GM_SO_LEAD).  EMQX_GM_SO_FLAG removes
  * nothing and marks (bit 4) every delivery for which ignore_local's fun returns
  * true: a session has all it needs to reproduce dropwhile bit for bit.
  * EMQX_GM_SO_DROP removes those deliveries (the order otherwise kept) and counts
@@ -883,6 +885,56 @@ int emqx_gm_deliveries_free(emqx_gm_ctx *ctx, emqx_gm_deliveries *d);
 int emqx_gm_subopts_info(const emqx_gm_subopts *so, emqx_gm_subopts_info_t *info);
 /* drops the table and its reference on the snapshot */
 int emqx_gm_subopts_release(emqx_gm_subopts *so);
+
+/* SESSION BATCHES (gm_batches.hip): the same deliveries ordered by SUBSCRIBER.
+ * In the reference every subscriber's connection process drains all
+ * {deliver, Filter, Msg} of its mailbox into one list (emqx_connection.erl:
+ * 516-520, emqx_misc:drain_deliver/1, emqx_misc.erl:159-173) and hands it to
+ * emqx_channel:handle_deliver/2 (emqx_channel.erl:830-842), which runs
+ * emqx_session:ignore_local/4 (emqx_session.erl:279-291) over the list and
+ * enriches what remains.  emqx_gm_deliver_batches gives a window as those lists.
+ * Number the window's deliveries k = 0, 1, ... in the order emqx_gm_deliver
+ * emits them in EMQX_GM_SO_FLAG mode (rows ascending, a row's filters in row
+ * order, a filter's subscribers in list order).  Subscriber S's BATCH is the
+ * deliveries with subscriber S in ascending k -- the order in which one
+ * dispatching process's sends reach S's mailbox; a subscriber under two
+ * filters of one row appears twice, adjacent, in the row's filter order.
+ * Batches are listed by ascending subscriber id; a subscriber is listed when
+ * it has a delivery BEFORE any removal.  Batch j is subs[j] with entries
+ * [batch_off[j], batch_off[j + 1]) of rows / filters / dopt: the window row,
+ * the filter id (the deliver's Topic) and the delivery byte.
+ * MODES: EMQX_GM_SO_FLAG removes nothing (bit 4 marks a hit); EMQX_GM_SO_DROP
+ * removes every hit (emqx_gm_deliver's rule); EMQX_GM_SO_LEAD -- valid for this
+ * call only -- removes from each batch exactly its LEADING run of hits and
+ * clears bit 4 in what it keeps: the window delivered as one batch per
+ * subscriber is a batch the library does know, and the result is bit-equal to
+ * ignore_local/4 followed by enrich_deliver/2 over it.  A batch emptied by
+ * removal stays listed (equal offsets) with its count in batch_dropped (the
+ * delivery.dropped.no_local metric).
+ * Inputs and refusals as emqx_gm_deliver's (host inputs fully checked before
+ * any device work; device rows skipped / clamped / masked); the result lives on
+ * the rows' side.  2^32 - 1 deliveries or more before removal:
+ * EMQX_GM_EOVERFLOW, decided by the counting pass before any output is sized.
+ * A failing call leaves `out` untouched.  An empty window, all-empty rows or a
+ * table without subscribers: a valid result with zero batches.  The result is
+ * deterministic.  The table lives on the first listed device of a multi-device
+ * context and the call runs there. */
+#define EMQX_GM_SO_LEAD 2u /* emqx_gm_deliver_batches only: remove each batch's leading run of hits */
+typedef struct {
+  uint64_t n_rows, n_deliveries /* kept, < 2^32 - 1 */, n_batches, n_dropped;
+  uint32_t *subs;          /* [n_batches] ascending, distinct                    */
+  uint64_t *batch_off;     /* [n_batches + 1]                                    */
+  uint32_t *rows;          /* [n_deliveries] window row                          */
+  uint32_t *filters;       /* [n_deliveries] filter id: the deliver's Topic      */
+  uint8_t  *dopt;          /* [n_deliveries] delivery byte                       */
+  uint32_t *batch_dropped; /* [n_batches] removed from the batch; NULL in FLAG   */
+  int32_t on_device; void *priv;
+} emqx_gm_batches;
+int emqx_gm_deliver_batches(emqx_gm_ctx *ctx, emqx_gm_subopts *so, const emqx_gm_csr *matches,
+                            const uint8_t *msg_flags, const uint32_t *msg_from, uint32_t mode,
+                            emqx_gm_batches *out);
+/* frees a result (ctx may be NULL for a result of emqx_gm_deliver_batches_host) */
+int emqx_gm_batches_free(emqx_gm_ctx *ctx, emqx_gm_batches *b);
 
 /* ---- a whole publish window in one device round trip (gm_publish.hip) ----
  * A broker node's unit of work is a publish window, and for every message of

@@ -15,7 +15,7 @@
 -export([load_retained/1, load_retained/2, match_retained/3, expire_retained/2]).
 -export([load_shared/3, load_shared/4, pick_shared/4, pick_shared_nif/5]).
 -export([publish_window/4, publish_window_nif/5]).
--export([load_subopts/3, deliver/5]).
+-export([load_subopts/3, deliver/5, deliver_batches/5]).
 -export([publish_window_deliver/7, publish_window_deliver_nif/9]).
 -export([load_authz/1, authorize_batch/2, authz_rule/2, authz_request/3, authorize/5]).
 -export([match/2]).
@@ -178,6 +178,18 @@ load_subopts(_Index, _Entries, _DefaultOpt) -> erlang:nif_error(nif_not_loaded).
 -spec deliver(reference(), [binary()], [0..15], [non_neg_integer()], 0 | 1) ->
           [{[{non_neg_integer(), 0..31}], non_neg_integer()}] | {error, term()}.
 deliver(_Table, _Topics, _MsgFlags, _From, _Mode) -> erlang:nif_error(nif_not_loaded).
+
+%% deliver_batches/5: the same window by SUBSCRIBER (emqx_gm_deliver_batches):
+%% [{SubId, [{Filter, {Row, Byte}}]}] by ascending SubId, each subscriber's
+%% deliveries in window order -- the list its connection process would drain
+%% from its mailbox (emqx_misc:drain_deliver/1) for emqx_channel:handle_deliver/2.
+%% Row is the 0-based position of the message in Topics.  Mode 2 applies
+%% emqx_session:ignore_local/4 itself: only the leading run of No-Local hits of a
+%% list is removed (bit 4 cleared in what stays); a list it empties stays as
+%% {SubId, []}.
+-spec deliver_batches(reference(), [binary()], [0..15], [non_neg_integer()], 0 | 1 | 2) ->
+          [{non_neg_integer(), [{binary(), {non_neg_integer(), 0..31}}]}] | {error, term()}.
+deliver_batches(_Table, _Topics, _MsgFlags, _From, _Mode) -> erlang:nif_error(nif_not_loaded).
 
 -spec pick_shared_nif(reference(), [binary()], 0..3, [non_neg_integer()], non_neg_integer()) ->
           [[{binary(), {non_neg_integer(), non_neg_integer()}}]] | {error, term()}.

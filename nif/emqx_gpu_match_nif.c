@@ -1271,6 +1271,82 @@ static ERL_NIF_TERM deliver_nif(ErlNifEnv *env, int argc, const ERL_NIF_TERM arg
   return result;
 }
 
+/* deliver_batches(Table, [Topic], [MsgFlags], [From], Mode :: 0 | 1 | 2) -> [{SubId, [{Filter, {Row, Byte}}]}]
+ * by ascending SubId: the window's local deliveries grouped by subscriber
+ * (emqx_gm_deliver_batches), each subscriber's in window order -- the list its
+ * connection process would drain from its mailbox (emqx_misc:drain_deliver/1)
+ * and hand to emqx_channel:handle_deliver/2.  Filter is the deliver's Topic,
+ * Row the 0-based position of the message in [Topic], Byte as deliver/5 gives
+ * it.  Mode 2 removes each list's leading run of No-Local hits, as
+ * emqx_session:ignore_local/4 does over a drained batch, and clears bit 4; a
+ * list it empties stays in the result as {SubId, []}.  Arguments otherwise as
+ * deliver/5 takes them. */
+static ERL_NIF_TERM deliver_batches_nif(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  gm_subopts_res *r;
+  uint8_t *tb, *mf;
+  uint64_t *to, n, i, j, k;
+  unsigned nf = 0, nfr = 0, mode, v = 0;
+  uint32_t *from;
+  emqx_gm_csr m;
+  emqx_gm_batches b;
+  ERL_NIF_TERM result, h, t;
+  int rc, ok = 1;
+  (void)argc;
+  if (!enif_get_resource(env, argv[0], SUBOPTS_RT, (void **)&r) || !enif_get_list_length(env, argv[2], &nf) ||
+      !enif_get_list_length(env, argv[3], &nfr) || !enif_get_uint(env, argv[4], &mode))
+    return enif_make_badarg(env);
+  if (!pack_topics(env, argv[1], &tb, &to, &n)) return enif_make_badarg(env);
+  if (nf != n || nfr != n) {
+    free_topics(tb, to);
+    return enif_make_badarg(env);
+  }
+  mf = enif_alloc(n ? n : 1);
+  from = enif_alloc(sizeof(uint32_t) * (n ? n : 1));
+  for (i = 0, t = argv[2]; ok && enif_get_list_cell(env, t, &h, &t); ++i) {
+    ok = enif_get_uint(env, h, &v) && v <= 255; /* (bits 4-7 and QoS 3: refused by the library) */
+    if (ok) mf[i] = (uint8_t)v;
+  }
+  for (i = 0, t = argv[3]; ok && enif_get_list_cell(env, t, &h, &t); ++i) {
+    ok = enif_get_uint(env, h, &v);
+    if (ok) from[i] = v;
+  }
+  if (!ok) {
+    enif_free(mf);
+    enif_free(from);
+    free_topics(tb, to);
+    return enif_make_badarg(env);
+  }
+  rc = emqx_gm_match(CTX, r->idx, tb, to, n, EMQX_GM_WITH_EXACT, &m);
+  free_topics(tb, to);
+  if (rc == EMQX_GM_OK) {
+    rc = emqx_gm_deliver_batches(CTX, r->so, &m, mf, from, mode, &b);
+    emqx_gm_csr_free(CTX, &m);
+  }
+  enif_free(mf);
+  enif_free(from);
+  if (rc != EMQX_GM_OK) return error_tuple(env, rc);
+  result = enif_make_list(env, 0);
+  for (j = b.n_batches; j > 0; --j) { /* (built back to front: the result ascends) */
+    ERL_NIF_TERM list = enif_make_list(env, 0);
+    for (k = b.batch_off[j]; k > b.batch_off[j - 1]; --k) {
+      const uint8_t *p = NULL;
+      uint64_t l = 0;
+      if (emqx_gm_index_filter(r->idx, b.filters[k - 1], &p, &l) != EMQX_GM_OK) {
+        emqx_gm_batches_free(CTX, &b);
+        return error_tuple(env, EMQX_GM_EINVAL);
+      }
+      list = enif_make_list_cell(env,
+                                 enif_make_tuple2(env, enif_make_resource_binary(env, r, p, l),
+                                                  enif_make_tuple2(env, enif_make_uint(env, b.rows[k - 1]),
+                                                                   enif_make_uint(env, b.dopt[k - 1]))),
+                                 list);
+    }
+    result = enif_make_list_cell(env, enif_make_tuple2(env, enif_make_uint(env, b.subs[j - 1]), list), result);
+  }
+  emqx_gm_batches_free(CTX, &b);
+  return result;
+}
+
 /* publish_window_deliver_nif(Shared, SubOpts, [Topic], Strategy :: 0..3, [Hash], Seed, [MsgFlags], [From],
  *                            Mode :: 0 | 1) -> [{{[{SubId, Byte}], Dropped}, [{Filter, {GroupId, MemberId}}]}]
  * per topic, in batch order: what deliver/5 gives for it and what pick_shared_nif/5
@@ -1395,6 +1471,7 @@ static ErlNifFunc funcs[] = {
     {"publish_window_nif", 5, publish_window_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"load_subopts", 3, load_subopts, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"deliver", 5, deliver_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"deliver_batches", 5, deliver_batches_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"publish_window_deliver_nif", 9, publish_window_deliver_nif, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"load_authz", 1, load_authz, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"authorize_batch", 2, authorize_batch, ERL_NIF_DIRTY_JOB_CPU_BOUND},
